@@ -1,10 +1,18 @@
 """Flagship benchmark (driver contract).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
-        --master-port P bench.py --gpus N --steps K --warmup W
+        --master-port P bench.py --gpus N --steps K --warmup W [--full]
 
 Metric (BASELINE.json): "all-reduce algbw (GB/s) @1GiB fp32 + DP4xTP2 fwd step time".
+
+A plain run measures the headline only: the ``coll`` phase sets up, picks the algorithm,
+warms up, times the K steps and prints the result line (``value``, ``ms_per_step``).
+``--full`` adds everything else described below: the secondary collectives and the tuning
+sweep of the ``coll`` phase, every other phase and the shared-GPU dry run.
+``--dump-outputs DIR`` writes the all-reduce result of the last timed step to
+``DIR/allreduce_out.npy`` (float32; a fixed seeded sample of the 1 GiB buffer).  The
+inputs are rank-valued, so the same arguments give the same arrays in every run.
 
 * A step = one out-of-place all-reduce (SUM) of a 1 GiB fp32 buffer through the
   framework's HAND-WRITTEN device all-reduce.  Buffers come from the symmetric heap
@@ -67,6 +75,21 @@ import time
 REPO = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, REPO)
 
+
+def _no_build_in_readonly_tree() -> None:
+    """The benchmark runs what ``build()`` left.  The package's loader takes a build lock in
+    the package directory even when nothing is stale; in a tree this user cannot write
+    (built by another user, or mounted read-only) that lock cannot be opened, so the loader
+    is told not to build (``CCMPI_NO_AUTOBUILD``, inherited by every rank and phase child):
+    it imports the built extensions, and a missing one is an import error."""
+    pkg = os.path.join(REPO, "collective_communication_mpi_amd")
+    locks = [os.path.join(pkg, f".{n}.buildlock") for n in ("host", "device")]
+    if not all(os.access(p, os.W_OK) for p in [pkg] + [p for p in locks if os.path.exists(p)]):
+        os.environ.setdefault("CCMPI_NO_AUTOBUILD", "1")
+
+
+_no_build_in_readonly_tree()
+
 GiB = 1 << 30
 XGMI_LINK_GBPS = 153.6  # MI355X xGMI, per link and direction (7 links x 153.6 = 1075 GB/s per GPU)
 METRIC = "all-reduce algbw (GB/s) @1GiB fp32 + DP4xTP2 fwd step time, 1/2/4/8 MI355X"
@@ -78,6 +101,12 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every secondary measurement (the phase table above); "
+                         "without it only the headline all-reduce is set up, warmed up and timed")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; a fixed sample "
+                         "of a large output)")
     ap.add_argument("--size-mb", type=int, default=1024)
     ap.add_argument("--algo", default="auto", help="auto | twoshot | push | ring | rhd | oneshot | fanout | ...")
     ap.add_argument("--tp", type=int, default=0, help="TP degree of the harness step (default 2 if N>=2)")
@@ -234,6 +263,11 @@ def plan_phases(args, size: int):
     return out
 
 
+def phases_to_run(args, size: int):
+    """What this run executes: only the headline's phase, or with ``--full`` the whole plan."""
+    return plan_phases(args, size) if args.full else [("coll", args.coll_timeout)]
+
+
 def empty_headline(args, size: int, why: str) -> dict:
     return {"metric": METRIC, "value": 0.0, "unit": "GB/s", "n_gpus": size, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": None, "higher_is_better": True, "scaling": "weak",
@@ -326,7 +360,7 @@ def supervise(args) -> int:
     cpus, bind_mode = phase_binding(world, rank, local)
     bound = world.allgather(format_cpu_list(cpus if cpus else os.sched_getaffinity(0)))
     status = {}
-    for phase, budget in plan_phases(args, size):
+    for phase, budget in phases_to_run(args, size):
         env = dict(os.environ, CCMPI_RANK=str(rank), CCMPI_SIZE=str(size), CCMPI_LOCAL_RANK=str(local),
                    CCMPI_LOCAL_SIZE=os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("CCMPI_LOCAL_SIZE", str(size))),
                    LOCAL_RANK=str(local), CCMPI_JOBID=f"{job}-{phase}", CCMPI_BENCH_WORKER="1",
@@ -380,7 +414,7 @@ def supervise(args) -> int:
         out = merge_results(args, size, status, load)
         if not status["coll"]["ok"] and not out.get("partial"):
             rc = 1
-        if size == 1 and args.shared_dry_run > 1 and not args.no_secondary:
+        if args.full and size == 1 and args.shared_dry_run > 1 and not args.no_secondary:
             out["config"]["shared_gpu_dry_run"] = shared_dry_run(args.shared_dry_run, steps=5, warmup=2,
                                                                  verbose=args.verbose)
         print(json.dumps(out), flush=True)
@@ -397,8 +431,8 @@ def shared_dry_run(n: int, steps: int, warmup: int, verbose: bool):
     map and the DP4xTP2 forward measured 1.6-7.0 ms instead of ~0.6 ms
     (profiles/r3_dryrun).  ``CCMPI_DRYRUN_HW_QUEUES`` overrides (empty = HIP default)."""
     cmd = [sys.executable, "-m", "collective_communication_mpi_amd.launch", "-n", str(n), "--timeout", "600",
-           sys.executable, os.path.abspath(__file__), "--gpus", str(n), "--steps", str(steps), "--warmup", str(warmup),
-           "--dp-layers", "0", "--a2a-mb", "64", "--shared-dry-run", "0", "--no-rccl", "--mlp-tokens", "0",
+           sys.executable, os.path.abspath(__file__), "--full", "--gpus", str(n), "--steps", str(steps),
+           "--warmup", str(warmup), "--dp-layers", "0", "--a2a-mb", "64", "--shared-dry-run", "0", "--no-rccl", "--mlp-tokens", "0",
            "--tune-max-mb", "16", "--host-ranks", "0"]
     env = dict(os.environ, CCMPI_BENCH_CHILD="1")
     # the placement an N-GPU run uses (every rank on its GPU's CPUs, a CCD each);
@@ -818,7 +852,9 @@ def coll_phase(args) -> dict:
     _fault_injection("coll")
     tuning = {}
     rec = coll_record(args, comm, r, tuning)
-    if not args.no_secondary:
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, r["y"])
+    if args.full and not args.no_secondary:
         # the fp32 headline is on disk before any secondary runs: a crash or hang in the
         # bf16 / all-to-all / tuning work below keeps ``value`` (marked partial)
         _write_result(args, rank, {**rec, "partial": "written after the fp32 headline, before the secondaries"})
@@ -847,6 +883,29 @@ def coll_phase(args) -> dict:
     r.pop("x", None), r.pop("y", None)
     torch.cuda.synchronize()
     return rec
+
+
+DUMP_SAMPLE = 1 << 22  # elements of a dumped array (16 MiB of float32)
+
+
+def dump_outputs(path: str, rank: int, y) -> None:
+    """``--dump-outputs``: rank 0 writes the all-reduce result of the last timed step (the
+    same on every rank) to ``allreduce_out.npy`` as float32.  An output larger than
+    ``DUMP_SAMPLE`` elements is sampled at fixed seeded positions (sorted, both ends
+    included), so two builds run with the same arguments write comparable arrays."""
+    if rank != 0:
+        return
+    import numpy as np
+    import torch
+
+    n = y.numel()
+    if n > DUMP_SAMPLE:
+        g = torch.Generator().manual_seed(0)
+        idx = torch.randint(0, n, (DUMP_SAMPLE,), generator=g).sort().values
+        idx[0], idx[-1] = 0, n - 1
+        y = y[idx.to(y.device)]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "allreduce_out.npy"), y.float().cpu().numpy())
 
 
 def coll_record(args, comm, r: dict, tuning: dict) -> dict:
@@ -1186,6 +1245,9 @@ def _write_result(args, rank: int, out: dict) -> None:
 
 def main() -> int:
     args = parse()
+    if args.dump_outputs and not os.path.isabs(args.dump_outputs):
+        # the ranks and phase children start in the repository: hand them the caller's directory
+        sys.argv += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     launched = any(k in os.environ for k in ("RANK", "CCMPI_RANK", "PMI_RANK", "OMPI_COMM_WORLD_RANK"))
     if args.gpus > 1 and not launched:
         return relaunch(args.gpus)

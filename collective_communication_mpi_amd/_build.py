@@ -59,11 +59,20 @@ class _Lock:
         self.path = PKG / f".{name}.buildlock"
 
     def __enter__(self):
-        self.fd = os.open(self.path, os.O_CREAT | os.O_RDWR, 0o644)
+        try:
+            self.fd = os.open(self.path, os.O_CREAT | os.O_RDWR, 0o644)
+        except OSError:
+            # a tree this user cannot write (built by another user, read-only mount): nobody
+            # here can build into it either, so there is nothing to serialise; an up-to-date
+            # target is returned as it is and a stale one fails in the build itself
+            self.fd = None
+            return self
         fcntl.flock(self.fd, fcntl.LOCK_EX)
         return self
 
     def __exit__(self, *exc):
+        if self.fd is None:
+            return
         fcntl.flock(self.fd, fcntl.LOCK_UN)
         os.close(self.fd)
 

@@ -9,6 +9,6 @@ timeout -k 10 700 python -u -m pytest tests -m gpu -x -v --timeout 400 --timeout
 rc=$?; echo "pytest rc=$rc"; tail -3 $OUT/pytest_gpu.log; [ $rc -ne 0 ] && { grep -E "FAILED|Error" $OUT/pytest_gpu.log | head; exit $rc; }
 timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1
 rc=$?; echo "smoke rc=$rc"; tail -2 $OUT/smoke.log; [ $rc -ne 0 ] && exit $rc
-timeout -k 10 500 python bench.py > $OUT/bench1.json 2> $OUT/bench1.err
+timeout -k 10 500 python bench.py --full > $OUT/bench1.json 2> $OUT/bench1.err
 rc=$?; echo "bench rc=$rc"; cut -c1-400 $OUT/bench1.json
 exit $rc

@@ -75,6 +75,37 @@ def test_phase_plan_isolates_harness():
     assert "fanout:1024" not in bench.allreduce_candidates(8, False)
 
 
+def test_plain_run_is_the_headline_phase_only():
+    """Without ``--full`` only the phase that measures ``value`` runs, at any N."""
+    plain = bench.parse(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert not plain.full and plain.steps == 3 and plain.warmup == 1
+    assert [p for p, _ in bench.phases_to_run(plain, 1)] == ["coll"]
+    assert [p for p, _ in bench.phases_to_run(plain, 8)] == ["coll"]
+    full = bench.parse(["--full"])
+    assert bench.phases_to_run(full, 8) == bench.plan_phases(full, 8)
+    assert [p for p, _ in bench.phases_to_run(full, 1)] == ["coll", "harness", "mlp", "host"]
+
+
+def test_dump_outputs_fixed_sample(tmp_path, monkeypatch):
+    """``--dump-outputs``: float32 ``.npy`` from rank 0 only; a large output is sampled at the
+    same sorted positions (both ends included) in every run."""
+    import numpy as np
+    import torch
+
+    y = torch.arange(1000, dtype=torch.float32)
+    bench.dump_outputs(str(tmp_path / "whole"), 0, y)
+    whole = np.load(tmp_path / "whole" / "allreduce_out.npy")
+    assert whole.dtype == np.float32 and np.array_equal(whole, y.numpy())
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 64)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), 0, y)
+    a, b = (np.load(tmp_path / d / "allreduce_out.npy") for d in ("a", "b"))
+    assert a.dtype == np.float32 and a.shape == (64,) and np.array_equal(a, b)
+    assert a[0] == 0 and a[-1] == 999 and np.all(np.diff(a) >= 0)
+    bench.dump_outputs(str(tmp_path / "rank1"), 1, y)
+    assert not (tmp_path / "rank1").exists()
+
+
 def test_multi_stream_graph_hazard(monkeypatch):
     """The HIP-graph guard of the harness: multi-stream forwards are not captured with fewer
     than 4 hardware queues per process (the runtime's parallel-stream crash)."""

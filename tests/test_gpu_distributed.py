@@ -138,7 +138,8 @@ def _bench_line(extra_env, *args):
     from _launch import REPO
 
     e = dict(os.environ, **ENV, **extra_env)
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--size-mb", "16",
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--gpus", "2", "--steps", "2", "--warmup", "1",
+                        "--size-mb", "16",
                         "--a2a-mb", "8", "--dp-layers", "0", "--batch", "128", "--no-secondary", *args],
                        cwd=REPO, env=e, capture_output=True, text=True, timeout=400)
     assert r.returncode == 0, r.stderr[-4000:]
@@ -180,7 +181,8 @@ def test_bench_tuning_crash_keeps_headline():
     from _launch import REPO
 
     e = dict(os.environ, **ENV, CCMPI_BENCH_FAULT="coll_tuning")
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--size-mb", "16",
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--gpus", "2", "--steps", "2", "--warmup", "1",
+                        "--size-mb", "16",
                         "--a2a-mb", "8", "--dp-layers", "0", "--batch", "128", "--tune-max-mb", "1", "--no-rccl",
                         "--no-harness", "--mlp-tokens", "0"], cwd=REPO, env=e, capture_output=True, text=True, timeout=400)
     assert r.returncode == 0, r.stderr[-4000:]
@@ -204,7 +206,8 @@ def test_bench_failing_candidates_keep_headline():
     # here (the collectives themselves take milliseconds at 16 MiB) instead of the suite's 20
     e = dict(os.environ, **ENV, CCMPI_BENCH_FAULT="candidate:twoshot:256,candidate_bf16:*")
     e["CCMPI_DEVICE_TIMEOUT_S"] = "6"
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--size-mb", "16",
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--gpus", "2", "--steps", "2", "--warmup", "1",
+                        "--size-mb", "16",
                         "--a2a-mb", "8", "--dp-layers", "0", "--tune-max-mb", "1", "--no-rccl", "--no-harness",
                         "--mlp-tokens", "0", "--host-ranks", "0"],
                        cwd=REPO, env=e, capture_output=True, text=True, timeout=400)
@@ -403,7 +406,8 @@ def test_bench_multi_rank_path_shared_gpu():
     from _launch import REPO
 
     e = dict(os.environ, **ENV)
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "4", "--steps", "3", "--warmup", "1", "--size-mb", "64",
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--gpus", "4", "--steps", "3", "--warmup", "1",
+                        "--size-mb", "64",
                         "--a2a-mb", "16", "--dp-layers", "1", "--dp-tokens", "1024", "--dp-vocab", "0", "--batch", "256",
                         "--mlp-tokens", "512"],
                        cwd=REPO, env=e, capture_output=True, text=True, timeout=400)
