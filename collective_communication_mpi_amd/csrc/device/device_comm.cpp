@@ -766,6 +766,75 @@ void DeviceComm::alltoallv_dev(uint64_t in, uint64_t counts, uint64_t out, uint6
   launch_alltoallv_dev(v, std::max(1, std::min(max_blocks > 0 ? max_blocks : 256, kMaxBlocks)), st);
 }
 
+// The (rank-invariant) shape rules shared by moe_dispatch and moe_combine.
+static void moe_check_shape(int size, int64_t T, int K, int E, uint64_t row_bytes) {
+  if (E < 1 || E > kMoeMaxExperts || E % size)
+    throw std::invalid_argument("ccmpi: moe needs 1 <= num_experts <= 256, a multiple of the group size");
+  if (K < 1 || K > kMoeMaxTopK) throw std::invalid_argument("ccmpi: moe needs 1 <= K <= 8");
+  if (T < 0 || T * K >= (1ll << 31)) throw std::invalid_argument("ccmpi: moe needs 0 <= T * K < 2^31");
+  if (row_bytes == 0 || row_bytes % 16 || row_bytes >= (1ull << 31))
+    throw std::invalid_argument("ccmpi: moe rows must be a 16-B multiple below 2 GiB");
+}
+
+void DeviceComm::moe_dispatch(uint64_t x, uint64_t idx, uint64_t recv_x, uint64_t recv_rows, uint64_t row_of,
+                              uint64_t expert_counts, uint64_t chunk_hist, int64_t T, int K, int E,
+                              uint64_t row_bytes, uint64_t stream, int max_blocks) {
+  moe_check_shape(size_, T, K, E, row_bytes);
+  if (x % 16 || recv_x % 16) throw std::invalid_argument("ccmpi: moe_dispatch buffers must be 16-B aligned");
+  if (recv_rows < 1 || recv_rows >= (1ull << 31))
+    throw std::invalid_argument("ccmpi: moe_dispatch needs 1 <= rows of recv_x < 2^31");
+  if (scratch_bytes() < 4ull * (E + 1)) throw std::runtime_error("ccmpi: scratch too small for the moe count row");
+  const uint64_t rc = code_of_(recv_x, recv_rows * row_bytes);
+  if (!rc) throw std::invalid_argument("ccmpi: moe_dispatch needs a registered (symmetric-heap) recv_x on every rank");
+  CCMPI_HIP_CHECK(hipSetDevice(device_));
+  hipStream_t st = S(stream);
+  MoEArgs m{};
+  m.a = args_(addr_code(0, 0), rc, nullptr, 0, 0);
+  m.a.in = reinterpret_cast<const char*>(x);
+  m.idx = reinterpret_cast<const int32_t*>(idx);
+  m.row_of = reinterpret_cast<int32_t*>(row_of);
+  m.expert_counts = reinterpret_cast<int64_t*>(expert_counts);
+  m.chunk_hist = reinterpret_cast<int32_t*>(chunk_hist);
+  // the count row is staged at the start of scratch by the routing kernel (stream-ordered
+  // before the dispatch; the previous collective that used scratch passed its final
+  // barrier on every rank)
+  m.count_row = reinterpret_cast<int32_t*>(scratch_ptr());
+  m.T = (int32_t)T;
+  m.K = K;
+  m.E = E;
+  m.El = E / size_;
+  m.row_bytes = (uint32_t)row_bytes;
+  m.cap = (int32_t)recv_rows;
+  launch_moe_route(m, st);
+  launch_moe_dispatch(m, std::max(1, std::min(max_blocks > 0 ? max_blocks : 256, kMaxBlocks)), st);
+}
+
+void DeviceComm::moe_combine(uint64_t y, uint64_t y_rows, uint64_t out, uint64_t idx, uint64_t row_of,
+                             uint64_t weights, int64_t T, int K, int E, uint64_t row_bytes, int dtype,
+                             uint64_t stream, int max_blocks) {
+  moe_check_shape(size_, T, K, E, row_bytes);
+  if (dtype != DT_F32 && dtype != DT_BF16 && dtype != DT_F16)
+    throw std::invalid_argument("ccmpi: moe_combine supports bf16, fp16 and fp32");
+  if (y % 16 || out % 16) throw std::invalid_argument("ccmpi: moe_combine buffers must be 16-B aligned");
+  if (y_rows < 1) throw std::invalid_argument("ccmpi: moe_combine needs at least one row of y");
+  const uint64_t yc = code_of_(y, y_rows * row_bytes);
+  if (!yc) throw std::invalid_argument("ccmpi: moe_combine needs a registered (symmetric-heap) y on every rank");
+  CCMPI_HIP_CHECK(hipSetDevice(device_));
+  hipStream_t st = S(stream);
+  MoEArgs m{};
+  m.a = args_(yc, 0, reinterpret_cast<char*>(out), 0, 0);
+  m.idx = reinterpret_cast<const int32_t*>(idx);
+  m.row_of = reinterpret_cast<int32_t*>(row_of);
+  m.weights = reinterpret_cast<const float*>(weights);
+  m.T = (int32_t)T;
+  m.K = K;
+  m.E = E;
+  m.El = E / size_;
+  m.row_bytes = (uint32_t)row_bytes;
+  m.dtype = dtype;
+  launch_moe_combine(m, std::max(1, std::min(max_blocks > 0 ? max_blocks : 256, kMaxBlocks)), st);
+}
+
 void DeviceComm::bcast(uint64_t buf, uint64_t nbytes, int root, uint64_t stream, int max_blocks, bool symmetric,
                        int mode) {
   DynScope dyn_scope(this, symmetric);

@@ -20,6 +20,7 @@
 #include "collectives.hpp"
 #include "common.hpp"
 #include "gemm_common.hpp"
+#include "moe.hpp"
 
 namespace ccmpi {
 namespace dev {
@@ -94,6 +95,20 @@ class DeviceComm {
                      int elem_bytes, uint64_t stream, int max_blocks);
   void alltoall(uint64_t in, uint64_t out, uint64_t bytes_per_peer, uint64_t stream, int max_blocks,
                 bool symmetric, int mode = 0);
+  // Routed MoE token dispatch (moe.hip): x [T, row_bytes] and idx [T, K] (int32 expert ids,
+  // -1 = dropped) are local; every routed (token, slot) row is pushed into the owner's
+  // registered recv_x [recv_rows, row_bytes] in (local expert, source rank, token, slot)
+  // order.  Outputs, all on the device: row_of [T, K] int32 (row taken, -1 = none),
+  // expert_counts [E / p] int64.  chunk_hist: int32 workspace of moe_chunks(T * K) * E.
+  // A row past the owner's capacity is not written (fault code 0xA00 + owner).
+  void moe_dispatch(uint64_t x, uint64_t idx, uint64_t recv_x, uint64_t recv_rows, uint64_t row_of,
+                    uint64_t expert_counts, uint64_t chunk_hist, int64_t T, int K, int E, uint64_t row_bytes,
+                    uint64_t stream, int max_blocks);
+  // Weighted combine (pull): out[t] = sum_k w[t, k] * y_owner(idx[t, k])[row_of[t, k]], fp32 in
+  // slot order, rounded once.  y [y_rows, row_bytes] registered on every rank; weights
+  // [T, K] fp32 or 0 (all ones); out local.
+  void moe_combine(uint64_t y, uint64_t y_rows, uint64_t out, uint64_t idx, uint64_t row_of, uint64_t weights,
+                   int64_t T, int K, int E, uint64_t row_bytes, int dtype, uint64_t stream, int max_blocks);
   // mode A2A_PUSH: symmetric buffers only, the root writes into every peer's buffer
   void bcast(uint64_t buf, uint64_t nbytes, int root, uint64_t stream, int max_blocks, bool symmetric, int mode = 0);
   void local_reduce(const std::vector<uint64_t>& ins, uint64_t out, uint64_t count, int dtype, int op,

@@ -126,6 +126,85 @@ def alltoallv_plan(counts, me: int, es: int):
     return soff, doff, [int(x) for x in b[me]], int(b.sum(axis=1).max())
 
 
+MOE_MAX_EXPERTS = 256
+MOE_MAX_TOPK = 8
+_MOE_CHUNK = 1024  # entries per routing chunk (csrc/device/moe.hpp kMoeChunk)
+
+
+def moe_layout(counts, me: int):
+    """Row layout of the routed MoE dispatch from the p x E count matrix
+    (``counts[i][e]`` = (token, slot) entries of rank i routed to expert e; expert e
+    lives on rank ``e // (E // p)``).  Every rank's receive buffer is ordered by
+    (local expert, source rank, source token, slot), so the rows of source i for
+    expert e form one segment.  Returns ``(base, expert_counts, totals)``:
+    ``base[i][e]`` = first row of that segment in the owner's buffer (p x E, the
+    segments of all ranks), ``expert_counts`` = rows per local expert of rank ``me``
+    (E // p), ``totals[j]`` = valid rows on rank j (p)."""
+    c = np.asarray(counts, dtype=np.int64)
+    if c.ndim != 2 or c.shape[0] < 1 or c.shape[1] % c.shape[0]:
+        raise ValueError("moe_layout: counts must be a p x E matrix with E a multiple of p")
+    if (c < 0).any():
+        raise ValueError("moe_layout: counts must be non-negative")
+    p, E = c.shape
+    if not 0 <= me < p:
+        raise ValueError("moe_layout: rank out of range")
+    El = E // p
+    col = c.sum(axis=0)                                  # rows of each expert
+    per_rank = col.reshape(p, El)
+    first = (np.cumsum(per_rank, axis=1) - per_rank).reshape(E)  # first row of expert e on its rank
+    before = np.cumsum(c, axis=0) - c                    # rows of sources < i for expert e
+    base = first[None, :] + before
+    return base, col[me * El:(me + 1) * El].copy(), per_rank.sum(axis=1)
+
+
+def moe_validate(p: int, x, topk_idx, num_experts: int, recv_x) -> Tuple[int, int, int]:
+    """Argument rules of ``moe_dispatch`` that need no GPU (shapes, dtypes, bounds);
+    raises ValueError, returns (T, K, D).  They depend on rank-invariant properties
+    only, so every rank raises together."""
+    import torch
+
+    E = int(num_experts)
+    if E < 1 or E > MOE_MAX_EXPERTS:
+        raise ValueError(f"moe_dispatch: num_experts must be in [1, {MOE_MAX_EXPERTS}], got {E}")
+    if E % p:
+        raise ValueError(f"moe_dispatch: num_experts ({E}) must be a multiple of the group size ({p})")
+    if x.dim() != 2 or topk_idx.dim() != 2 or recv_x.dim() != 2:
+        raise ValueError("moe_dispatch: x [T, D], topk_idx [T, K] and recv_x [cap, D] must be 2-D")
+    T, D = x.shape
+    K = topk_idx.shape[1]
+    if topk_idx.shape[0] != T:
+        raise ValueError(f"moe_dispatch: topk_idx has {topk_idx.shape[0]} rows, x has {T}")
+    if K < 1 or K > MOE_MAX_TOPK:
+        raise ValueError(f"moe_dispatch: K must be in [1, {MOE_MAX_TOPK}], got {K}")
+    if x.dtype not in (torch.bfloat16, torch.float16, torch.float32):
+        raise ValueError(f"moe_dispatch: x must be bf16, fp16 or fp32, got {x.dtype}")
+    if topk_idx.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"moe_dispatch: topk_idx must be int32 or int64, got {topk_idx.dtype}")
+    if recv_x.dtype != x.dtype or recv_x.shape[1] != D:
+        raise ValueError("moe_dispatch: recv_x must have x's dtype and row length")
+    if D < 1 or (D * x.element_size()) % 16:
+        raise ValueError("moe_dispatch: rows must be a non-empty multiple of 16 bytes")
+    if recv_x.shape[0] < 1:
+        raise ValueError("moe_dispatch: recv_x needs at least one row")
+    if T * K >= 1 << 31:
+        raise ValueError("moe_dispatch: T * K must be below 2^31")
+    return int(T), int(K), int(D)
+
+
+class MoEHandle:
+    """What ``moe_dispatch`` leaves for ``moe_combine``: device tensors only.
+
+    ``row_of`` [T, K] int32: the row each (token, slot) took in its expert's rank's
+    buffer (-1: dropped, or refused for lack of capacity); ``topk_idx`` [T, K] as
+    int32; ``expert_counts`` [E // p] int64: rows per local expert on this rank."""
+
+    __slots__ = ("row_of", "topk_idx", "expert_counts", "num_experts", "T", "K", "D", "dtype", "cap")
+
+    def __init__(self, row_of, topk_idx, expert_counts, num_experts, T, K, D, dtype, cap) -> None:
+        self.row_of, self.topk_idx, self.expert_counts = row_of, topk_idx, expert_counts
+        self.num_experts, self.T, self.K, self.D, self.dtype, self.cap = num_experts, T, K, D, dtype, cap
+
+
 def stale_keys(keys, key) -> List[tuple]:
     """On-demand registration slots that ``key`` invalidates: a slot is keyed by one
     (IPC handle, allocation base, bytes, allocator generation) per rank; it is stale
@@ -1124,6 +1203,79 @@ class DeviceGroup:
         self.dc.alltoallv_dev(src.data_ptr(), counts.data_ptr(), dst.data_ptr(), dst.numel(), recv_counts.data_ptr(),
                               src.element_size(), s, self._budget(max_blocks))
         return dst
+
+    @trace_call("moe_dispatch")
+    def moe_dispatch(self, x, topk_idx, num_experts: int, recv_x, max_blocks: Optional[int] = None) -> MoEHandle:
+        """Routed MoE token dispatch: the router's output goes in, expert-grouped rows
+        come out.  ``num_experts`` E (<= 256, a multiple of p) experts, E // p consecutive
+        ones per rank (expert e lives on rank ``e // (E // p)``).  ``x`` [T, D] (bf16 /
+        fp16 / fp32, rows a 16-B multiple, 16-B aligned base) and ``topk_idx`` [T, K]
+        (int32 / int64, K <= 8, -1 = slot dropped) are local; T may differ per rank and
+        be 0.  ``recv_x`` [cap, D] comes from the symmetric heap (``comm.empty``) on every
+        rank.  Afterwards it holds one row per (token, slot) routed to a local expert, in
+        lexicographic order of (local expert, source rank, source token, slot) -- the
+        rows of one expert are contiguous, whatever the scheduling.  The kernels route
+        on the device (``k_moe_hist`` / ``k_moe_rank``), exchange the count rows themselves
+        and push each token once per routed slot straight into the owner's buffer
+        (``k_moe_dispatch``): no host synchronisation, capturable in a HIP graph.
+        Returns a :class:`MoEHandle` (``row_of``, ``expert_counts``, ...).  A row that
+        would land at or past ``cap`` is not written, its ``row_of`` stays -1 and
+        ``check()`` raises on the sender (fault code 0xA00 + owner)."""
+        torch = self.torch
+        T, K, D = moe_validate(self.size, x, topk_idx, num_experts, recv_x)
+        self._check(x, "x")
+        self._check(topk_idx, "topk_idx")
+        self._check(recv_x, "recv_x")
+        if x.data_ptr() % 16 or recv_x.data_ptr() % 16:
+            raise ValueError("moe_dispatch: x and recv_x must be 16-B aligned")
+        if not self.is_symmetric(recv_x):
+            raise ValueError("moe_dispatch: recv_x must come from the symmetric heap (comm.empty)")
+        E = int(num_experts)
+        idx = topk_idx if topk_idx.dtype == torch.int32 else topk_idx.to(torch.int32)
+        row_of = torch.empty((T, K), dtype=torch.int32, device=self.device)
+        expert_counts = torch.empty(E // self.size, dtype=torch.int64, device=self.device)
+        chunks = (T * K + _MOE_CHUNK - 1) // _MOE_CHUNK
+        hist = torch.empty(max(1, chunks * E), dtype=torch.int32, device=self.device)
+        s = self._stream()
+        self.dc.moe_dispatch(x.data_ptr(), idx.data_ptr(), recv_x.data_ptr(), recv_x.shape[0], row_of.data_ptr(),
+                             expert_counts.data_ptr(), hist.data_ptr(), T, K, E, D * x.element_size(), s,
+                             self._budget(max_blocks))
+        return MoEHandle(row_of, idx, expert_counts, E, T, K, D, x.dtype, int(recv_x.shape[0]))
+
+    @trace_call("moe_combine")
+    def moe_combine(self, y, handle: MoEHandle, weights=None, out=None, max_blocks: Optional[int] = None):
+        """Weighted combine, the way back of :meth:`moe_dispatch`: ``y`` [cap, D] (symmetric
+        heap, the expert outputs in ``recv_x``'s row order, at least as many rows as
+        ``recv_x`` had) on every rank gives, on the source rank,
+        ``out[t] = sum_{k: idx[t,k] >= 0} w[t,k] * y_owner(idx[t,k])[row_of[t,k]]``,
+        accumulated in fp32 in slot order k = 0..K-1 and rounded once (deterministic).
+        ``weights`` [T, K] fp32, or None for all ones; a token with no routed slot gives
+        a zero row.  One pull kernel (``k_moe_combine``): no atomics, no [T * K, D]
+        staging, no host synchronisation.  Returns ``out`` (allocated if None)."""
+        torch = self.torch
+        h = handle
+        self._check(y, "y")
+        if y.dim() != 2 or y.shape[1] != h.D or y.dtype != h.dtype:
+            raise ValueError("moe_combine: y must be [cap, D] with the dispatch's dtype and row length")
+        if y.shape[0] < h.cap:
+            raise ValueError(f"moe_combine: y has {y.shape[0]} rows, the dispatch buffer had {h.cap}")
+        if y.data_ptr() % 16 or not self.is_symmetric(y):
+            raise ValueError("moe_combine: y must come from the symmetric heap (comm.empty)")
+        if weights is not None:
+            self._check(weights, "weights")
+            if weights.dtype != torch.float32 or tuple(weights.shape) != (h.T, h.K):
+                raise ValueError("moe_combine: weights must be [T, K] fp32")
+        if out is None:
+            out = torch.empty((h.T, h.D), dtype=h.dtype, device=self.device)
+        else:
+            self._check(out, "out")
+            if out.dtype != h.dtype or tuple(out.shape) != (h.T, h.D) or out.data_ptr() % 16:
+                raise ValueError("moe_combine: out must be [T, D] of the dispatch's dtype, 16-B aligned")
+        s = self._stream()
+        self.dc.moe_combine(y.data_ptr(), y.shape[0], out.data_ptr(), h.topk_idx.data_ptr(), h.row_of.data_ptr(),
+                            0 if weights is None else weights.data_ptr(), h.T, h.K, h.num_experts,
+                            h.D * y.element_size(), dtype_code(h.dtype), s, self._budget(max_blocks))
+        return out
 
     @trace_call("bcast")
     def bcast(self, buf, root: int = 0, algo: str = "auto"):
