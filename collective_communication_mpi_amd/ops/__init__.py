@@ -14,4 +14,9 @@ from .kernels import (  # noqa: F401
     transpose,
     interleave_lastaxis,
     deinterleave_lastaxis,
+    grouped_gemm_nt,
+    grouped_gemm_tn,
+    grouped_linear,
+    grouped_validate,
+    grouped_tile_map,
 )

@@ -330,3 +330,174 @@ def deinterleave_lastaxis(x: torch.Tensor, p: int) -> torch.Tensor:
     out = torch.empty(p, *x.shape[:-1], k, dtype=x.dtype, device=x.device)
     _D().deinterleave_lastaxis(x.data_ptr(), out.data_ptr(), M, p, k * x.element_size(), _stream(x))
     return out
+
+
+# ---------------------------------------------------------------------------
+# grouped expert GEMM over routed MoE rows (csrc/device/grouped_gemm.hip)
+# ---------------------------------------------------------------------------
+GROUPED_MAX_EXPERTS = 256  # = device.MOE_MAX_EXPERTS: one count per thread of the kernel's scan
+GROUPED_BM = 128           # rows per tile
+
+
+def grouped_tile_map(counts, cap: int, bm: int = GROUPED_BM):
+    """Host mirror of the grouped kernels' tile walk: the ``(expert, first_row, rows)`` of
+    every row tile, in the order the kernel numbers them.  Expert g owns rows
+    ``[off_g, off_g + c_g)`` with ``c_g = max(counts[g], 0)`` and ``off_g`` their prefix sum,
+    both ends clamped to ``cap``; its tiles start at ``off_g`` (so no tile spans two experts)
+    and the last one is short.  There are at most ``ceil(cap / bm) + len(counts)`` tiles,
+    which is the row-tile count the forward kernel's grid is sized for."""
+    cap, bm = int(cap), int(bm)
+    if bm < 1:
+        raise ValueError("grouped_tile_map: bm must be positive")
+    tiles = []
+    at = 0
+    for g, c in enumerate(counts):
+        off = min(at, cap)
+        at += min(max(int(c), 0), max(cap, 0))
+        end = min(at, cap)
+        for r0 in range(off, end, bm):
+            tiles.append((g, r0, min(bm, end - r0)))
+    return tiles
+
+
+def grouped_validate(x, w, counts, out=None, bias=None, out_dtype=torch.bfloat16):
+    """Argument rules of ``grouped_gemm_nt`` that need no GPU; raises TypeError (dtypes) /
+    ValueError (shapes, strides, bounds) like ``gemm_nt`` and returns ``(cap, G, N, K)``.
+    ``w`` is ``[G, N, K]`` with unit inner stride; its other two strides are free (multiples
+    of 8 elements), so the ``[G, K, N]`` view of one transposed ``[K, G * N]`` copy is accepted."""
+    if x.dtype != torch.bfloat16 or w.dtype != torch.bfloat16:
+        raise TypeError("grouped GEMM expects bf16 operands")
+    if x.dim() != 2 or w.dim() != 3 or x.shape[1] != w.shape[2]:
+        raise ValueError(f"grouped GEMM shape mismatch: x {tuple(x.shape)}, w {tuple(w.shape)} (want [cap, K], [G, N, K])")
+    cap, K = x.shape
+    G, N = w.shape[0], w.shape[1]
+    if G < 1 or G > GROUPED_MAX_EXPERTS:
+        raise ValueError(f"grouped GEMM: the number of experts must be in [1, {GROUPED_MAX_EXPERTS}], got {G}")
+    if K < 8 or N < 8 or K % 8 or N % 8:
+        raise ValueError(f"grouped GEMM: K ({K}) and N ({N}) must be positive multiples of 8")
+    if x.stride(1) != 1 or w.stride(2) != 1:
+        raise ValueError("grouped GEMM operands must have unit inner stride")
+    if (cap > 1 and x.stride(0) % 8) or (N > 1 and w.stride(1) % 8) or (G > 1 and w.stride(0) % 8):
+        raise ValueError("grouped GEMM: row and expert strides must be multiples of 8 elements (16 bytes)")
+    if x.data_ptr() % 16 or w.data_ptr() % 16:
+        raise ValueError("grouped GEMM: operands must be 16-B aligned")
+    if counts.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"grouped GEMM: counts must be int32 or int64, got {counts.dtype}")
+    if counts.dim() != 1 or counts.shape[0] != G or not counts.is_contiguous():
+        raise ValueError(f"grouped GEMM: counts must be a contiguous [{G}] tensor, got {tuple(counts.shape)}")
+    if counts.device != x.device or w.device != x.device:
+        raise ValueError("grouped GEMM: x, w and counts must be on the same device")
+    if out is not None:
+        if out.dtype not in (torch.bfloat16, torch.float32):
+            raise TypeError("grouped GEMM output must be bf16 or fp32")
+        if out.shape != (cap, N) or out.stride(1) != 1 or out.device != x.device:
+            raise ValueError("grouped GEMM output must be [cap, N] with unit column stride on x's device")
+        if out.data_ptr() % 16 or (cap > 1 and (out.stride(0) * out.element_size()) % 16):
+            raise ValueError("grouped GEMM output rows must be 16-B aligned")
+    elif out_dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError("grouped GEMM output must be bf16 or fp32")
+    if bias is not None:
+        if bias.dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError("grouped GEMM bias must be fp32 or bf16")
+        if bias.shape != (G, N) or not bias.is_contiguous() or bias.device != x.device:
+            raise ValueError("grouped GEMM bias must be a contiguous [G, N] tensor on x's device")
+    return int(cap), int(G), int(N), int(K)
+
+
+def grouped_gemm_nt(x: torch.Tensor, w: torch.Tensor, counts: torch.Tensor, out: Optional[torch.Tensor] = None,
+                    bias: Optional[torch.Tensor] = None, alpha: float = 1.0,
+                    out_dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+    """``out[r] = alpha * x[r] @ w[g].T (+ bias[g])`` for every row r of expert g, the rows
+    per expert read from the device tensor ``counts`` (``moe_dispatch``'s ``expert_counts``):
+    no host synchronisation, a grid that does not depend on the counts, capturable in a graph.
+
+    x: [cap, K] bf16 (row stride free), w: [G, N, K] bf16, counts: [G] int32 / int64 on the
+    device, bias: [G, N] fp32 / bf16, out: [cap, N] bf16 or fp32.  Expert g owns rows
+    ``[off_g, off_g + c_g)``, ``c_g = max(counts[g], 0)``, ``off_g`` their prefix sum; the
+    ranges are clamped to cap (counts adding up to more truncate the last experts).  Rows at
+    or past ``sum(c_g)`` are left untouched: with ``out=None`` they are uninitialised."""
+    cap, G, N, K = grouped_validate(x, w, counts, out, bias, out_dtype)
+    if out is None:
+        out = torch.empty((cap, N), dtype=out_dtype, device=x.device)
+    bias_kind = 0 if bias is None else (1 if bias.dtype == torch.float32 else 2)
+    _D().grouped_gemm_nt(x.data_ptr(), w.data_ptr(), out.data_ptr(), 0 if bias is None else bias.data_ptr(),
+                         counts.data_ptr(), cap, N, K, G, x.stride(0) if cap > 1 else K, w.stride(1), w.stride(0),
+                         out.stride(0) if cap > 1 else N, N, float(alpha), bias_kind, out.dtype == torch.bfloat16,
+                         counts.dtype == torch.int64, _stream(x))
+    return out
+
+
+def grouped_gemm_tn(dy: torch.Tensor, x: torch.Tensor, counts: torch.Tensor, out: Optional[torch.Tensor] = None,
+                    alpha: float = 1.0) -> torch.Tensor:
+    """Weight gradients of ``grouped_gemm_nt``: ``out[g] = alpha * dy[rows of g].T @ x[rows of g]``,
+    fp32 ``[G, N, K]`` (dy [cap, N], x [cap, K] bf16, same row rules).  Both operands are read
+    row-major through ds_read_b64_tr_b16; rows outside an expert are masked at the load (they
+    may hold anything, NaN included); an expert with no rows gets zeros.  One workgroup per
+    (expert, 128 x 128 tile) walks the expert's rows in order: deterministic, no atomics."""
+    if dy.dtype != torch.bfloat16 or x.dtype != torch.bfloat16:
+        raise TypeError("grouped_gemm_tn expects bf16 operands")
+    if dy.dim() != 2 or x.dim() != 2 or dy.shape[0] != x.shape[0] or dy.stride(1) != 1 or x.stride(1) != 1:
+        raise ValueError(f"grouped_gemm_tn shape mismatch: {tuple(dy.shape)}^T x {tuple(x.shape)}")
+    if counts.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"grouped_gemm_tn: counts must be int32 or int64, got {counts.dtype}")
+    G = counts.numel()
+    if counts.dim() != 1 or not counts.is_contiguous() or G < 1 or G > GROUPED_MAX_EXPERTS:
+        raise ValueError(f"grouped_gemm_tn: counts must be a contiguous [G] tensor, 1 <= G <= {GROUPED_MAX_EXPERTS}")
+    if counts.device != x.device or dy.device != x.device:
+        raise ValueError("grouped_gemm_tn: dy, x and counts must be on the same device")
+    cap, N = dy.shape
+    K = x.shape[1]
+    if N < 8 or K < 8 or N % 8 or K % 8:
+        raise ValueError(f"grouped_gemm_tn: N ({N}) and K ({K}) must be positive multiples of 8")
+    if out is None:
+        out = torch.empty((G, N, K), dtype=torch.float32, device=x.device)
+    if out.dtype != torch.float32 or out.shape != (G, N, K) or out.stride(2) != 1 or out.device != x.device:
+        raise ValueError("grouped_gemm_tn output must be fp32 [G, N, K] with unit inner stride")
+    _D().grouped_gemm_tn(dy.data_ptr(), x.data_ptr(), out.data_ptr(), counts.data_ptr(), cap, N, K, G,
+                         dy.stride(0) if cap > 1 else N, x.stride(0) if cap > 1 else K, out.stride(1), out.stride(0),
+                         float(alpha), counts.dtype == torch.int64, _stream(x))
+    return out
+
+
+def _transposed_experts(w: torch.Tensor) -> torch.Tensor:
+    """``[G, K, N]`` view of one transposed copy of ``w`` [G, N, K]: the existing 2-D transpose
+    kernel turns the [G * N, K] matrix into [K, G * N]; expert g's w[g].T is its column block
+    g (row stride G * N), which ``grouped_gemm_nt`` reads through w's strides."""
+    G, N, K = w.shape
+    wt = transpose(w.contiguous().view(G * N, K))
+    return wt.view(K, G, N).permute(1, 0, 2)
+
+
+class _GroupedLinear(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, counts):
+        wb = w if w.dtype == torch.bfloat16 else w.to(torch.bfloat16)
+        ctx.save_for_backward(x, wb, counts)
+        ctx.w_dtype = w.dtype
+        return grouped_gemm_nt(x, wb, counts)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, wb, counts = ctx.saved_tensors
+        ok = dy.stride(1) == 1 and (dy.shape[0] <= 1 or dy.stride(0) % 8 == 0) and dy.data_ptr() % 16 == 0
+        dy = dy if ok else dy.contiguous()
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = grouped_gemm_nt(dy, _transposed_experts(wb), counts, out_dtype=x.dtype)
+        if ctx.needs_input_grad[1]:
+            dw = grouped_gemm_tn(dy, x, counts).to(ctx.w_dtype)
+        return dx, dw, None
+
+
+def grouped_linear(x: torch.Tensor, w: torch.Tensor, counts: torch.Tensor) -> torch.Tensor:
+    """Differentiable ``grouped_gemm_nt(x, w, counts)`` (bf16 out).  ``w`` is bf16, or fp32
+    master weights (rounded to bf16 for the kernels; their gradient then keeps the fp32 the
+    weight-gradient kernel computes).  Backward: dX is the forward kernel on a transposed copy
+    of the weights (one ``transpose`` launch over [G * N, K]; the kernel has no K-major-B
+    path), dW is ``grouped_gemm_tn`` in w's dtype; ``counts`` gets no gradient.  Neither
+    direction synchronises with the host.  Like the forward's output, dX is written for the
+    rows of the experts only: gradient rows at or past ``sum(counts)`` are unspecified
+    (uninitialised memory), as are the output's."""
+    if w.dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError("grouped_linear weights must be bf16 or fp32")
+    return _GroupedLinear.apply(x, w, counts)

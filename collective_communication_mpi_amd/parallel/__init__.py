@@ -20,3 +20,4 @@ from .tensor_parallel import (  # noqa: F401,E402
     reduce_from_tensor_parallel_region,
     scatter_to_tensor_parallel_region,
 )
+from .moe_experts import GroupedExpertsMLP  # noqa: F401,E402
