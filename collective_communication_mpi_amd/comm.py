@@ -241,6 +241,15 @@ class Communicator(object):
             raise TypeError("moe_combine runs on the device plane: y must be a CUDA tensor")
         return self.dev.moe_combine(y, handle, weights, out, max_blocks)
 
+    def moe_combine_backward(self, dout, handle, weights=None, y=None, dy=None, max_blocks=None):
+        """Backward of ``moe_combine`` (``DeviceGroup.moe_combine_backward``): ``dout`` goes
+        in, ``(dy, dweights)`` come out -- ``dy`` in the owners' symmetric buffers,
+        ``dweights`` only when the forward's ``y`` is given.  ``total_bytes_transferred``
+        is not advanced: the counts never reach the host."""
+        if not _is_device(dout):
+            raise TypeError("moe_combine_backward runs on the device plane: dout must be a CUDA tensor")
+        return self.dev.moe_combine_backward(dout, handle, weights, y, dy, max_blocks)
+
     def Bcast(self, buf, root: int = 0):
         isz, n = _nbytes_items(buf)
         if self.comm.Get_rank() == root:

@@ -151,6 +151,7 @@ PYBIND11_MODULE(_device, m) {
       .def("alltoallv", &DeviceComm::alltoallv, py::call_guard<py::gil_scoped_release>())
       .def("moe_dispatch", &DeviceComm::moe_dispatch, py::call_guard<py::gil_scoped_release>())
       .def("moe_combine", &DeviceComm::moe_combine, py::call_guard<py::gil_scoped_release>())
+      .def("moe_combine_bwd", &DeviceComm::moe_combine_bwd, py::call_guard<py::gil_scoped_release>())
       .def("alltoall", &DeviceComm::alltoall, py::arg("inp"), py::arg("out"), py::arg("bytes_per_peer"),
            py::arg("stream"), py::arg("max_blocks"), py::arg("symmetric"), py::arg("mode") = 0,
            py::call_guard<py::gil_scoped_release>())

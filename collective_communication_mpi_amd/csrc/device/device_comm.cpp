@@ -835,6 +835,43 @@ void DeviceComm::moe_combine(uint64_t y, uint64_t y_rows, uint64_t out, uint64_t
   launch_moe_combine(m, std::max(1, std::min(max_blocks > 0 ? max_blocks : 256, kMaxBlocks)), st);
 }
 
+void DeviceComm::moe_combine_bwd(uint64_t dout, uint64_t y, uint64_t y_rows, uint64_t dy, uint64_t dy_rows,
+                                 uint64_t dweights, uint64_t idx, uint64_t row_of, uint64_t weights, int64_t T, int K, int E,
+                                 uint64_t row_bytes, int dtype, uint64_t stream, int max_blocks) {
+  moe_check_shape(size_, T, K, E, row_bytes);
+  if (dtype != DT_F32 && dtype != DT_BF16 && dtype != DT_F16)
+    throw std::invalid_argument("ccmpi: moe_combine_backward supports bf16, fp16 and fp32");
+  if (dout % 16 || y % 16 || dy % 16)
+    throw std::invalid_argument("ccmpi: moe_combine_backward buffers must be 16-B aligned");
+  if (dy_rows < 1 || (y && y_rows < 1))
+    throw std::invalid_argument("ccmpi: moe_combine_backward needs at least one row of y and dy");
+  // an empty dweights (T == 0) has no address: such a rank still publishes its y for the peers
+  if ((dweights && !y) || (y && !dweights && T > 0))
+    throw std::invalid_argument("ccmpi: moe_combine_backward needs y and dweights together");
+  const uint64_t dc = code_of_(dy, dy_rows * row_bytes);
+  if (!dc)
+    throw std::invalid_argument("ccmpi: moe_combine_backward needs a registered (symmetric-heap) dy on every rank");
+  const uint64_t yc = y ? code_of_(y, y_rows * row_bytes) : 0;
+  if (y && !yc)
+    throw std::invalid_argument("ccmpi: moe_combine_backward needs a registered (symmetric-heap) y on every rank");
+  CCMPI_HIP_CHECK(hipSetDevice(device_));
+  hipStream_t st = S(stream);
+  MoEArgs m{};
+  m.a = args_(yc, dc, nullptr, 0, 0);
+  m.a.in = reinterpret_cast<const char*>(dout);
+  m.idx = reinterpret_cast<const int32_t*>(idx);
+  m.row_of = reinterpret_cast<int32_t*>(row_of);
+  m.weights = reinterpret_cast<const float*>(weights);
+  m.dweights = reinterpret_cast<float*>(dweights);
+  m.T = (int32_t)T;
+  m.K = K;
+  m.E = E;
+  m.El = E / size_;
+  m.row_bytes = (uint32_t)row_bytes;
+  m.dtype = dtype;
+  launch_moe_combine_bwd(m, std::max(1, std::min(max_blocks > 0 ? max_blocks : 256, kMaxBlocks)), st);
+}
+
 void DeviceComm::bcast(uint64_t buf, uint64_t nbytes, int root, uint64_t stream, int max_blocks, bool symmetric,
                        int mode) {
   DynScope dyn_scope(this, symmetric);

@@ -109,6 +109,14 @@ class DeviceComm {
   // [T, K] fp32 or 0 (all ones); out local.
   void moe_combine(uint64_t y, uint64_t y_rows, uint64_t out, uint64_t idx, uint64_t row_of, uint64_t weights,
                    int64_t T, int K, int E, uint64_t row_bytes, int dtype, uint64_t stream, int max_blocks);
+  // Backward of the weighted combine (push + pull in one kernel): dy_owner[row_of[t, k]] =
+  // w[t, k] * dout[t] (a copy with weights = 0) into the registered dy [dy_rows, row_bytes] of every
+  // rank, and, when dweights is not 0, dweights[t, k] = <dout[t], y_owner[row_of[t, k]]> (fp32,
+  // 0 for a slot that is not routed) from the registered y [y_rows, row_bytes].  y = 0 with
+  // dweights = 0: nothing is pulled.
+  void moe_combine_bwd(uint64_t dout, uint64_t y, uint64_t y_rows, uint64_t dy, uint64_t dy_rows,
+                       uint64_t dweights, uint64_t idx, uint64_t row_of, uint64_t weights, int64_t T, int K, int E,
+                       uint64_t row_bytes, int dtype, uint64_t stream, int max_blocks);
   // mode A2A_PUSH: symmetric buffers only, the root writes into every peer's buffer
   void bcast(uint64_t buf, uint64_t nbytes, int root, uint64_t stream, int max_blocks, bool symmetric, int mode = 0);
   void local_reduce(const std::vector<uint64_t>& ins, uint64_t out, uint64_t count, int dtype, int op,

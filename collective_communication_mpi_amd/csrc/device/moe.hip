@@ -25,6 +25,17 @@
 //                          token issues the loads of its K rows (peer memory) before
 //                          the fp32 multiply-add chain in slot order, rounds once and
 //                          stores out[t].  No atomics, no [T * K, D] staging.
+//   combine backward       k_moe_combine_bwd: the start barrier publishes y (read from
+//   (collective)           peers) and dy (written into peers); one wave per token loads
+//                          dout[t] once, pushes w[t,k] * dout[t] (one fp32 multiply, one
+//                          rounding; a plain copy without weights) into the owner's dy at
+//                          row_of[t,k], and, when dweights is wanted, pulls the K rows of y
+//                          for dweights[t,k] = <dout[t], y row>: fp32 per lane in vector
+//                          order, then a fixed butterfly over the wave (reproducible).
+//                          Rows are a bijection, so every routed row of dy is written once;
+//                          rows past a rank's total stay untouched.  An owner that published
+//                          no y while this rank pulls: its dy rows are read instead (in
+//                          bounds) and the call fails (fault code 0xD00 + owner).
 //
 // The grid is the same on every rank (CTA b pairs with CTA b of the peers); T may
 // differ per rank and be 0, such a rank still runs the barriers.
@@ -298,6 +309,138 @@ __global__ void __launch_bounds__(kThreads) k_moe_combine(MoEArgs m) {
   finish(a, e0);
 }
 
+// ---------------------------------------------------------------------------
+// combine backward
+// ---------------------------------------------------------------------------
+// Sum over the 64 lanes in a fixed butterfly: every lane ends with the same bits,
+// whatever the scheduling.
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s, 64);
+  return v;
+}
+
+template <int DT, bool PULL>
+__global__ void __launch_bounds__(kThreads) k_moe_combine_bwd(MoEArgs m) {
+  __shared__ uint64_t s_epoch;
+  __shared__ uint64_t codes[2][kMaxRanks];
+  __shared__ char* s_y[kMaxRanks];
+  __shared__ char* s_dy[kMaxRanks];
+  const CollArgs& a = m.a;
+  const PeerTable* pt = a.pt;
+  if (!start_phase(a, &s_epoch, codes)) return;
+  const uint64_t e0 = s_epoch;
+  const int nr = pt->size, E = m.E, El = m.El, K = m.K;
+  if (threadIdx.x < nr) {
+    s_dy[threadIdx.x] = resolve(pt, threadIdx.x, codes[1][threadIdx.x]);
+    s_y[threadIdx.x] = nullptr;
+    if (PULL) {
+      if (codes[0][threadIdx.x]) {
+        s_y[threadIdx.x] = resolve(pt, threadIdx.x, codes[0][threadIdx.x]);
+      } else {  // that rank was given no y (code 0): its dy rows are read instead, in bounds, and the call fails
+        s_y[threadIdx.x] = s_dy[threadIdx.x];
+        __hip_atomic_store(&pt->sig[pt->rank]->error, 0xD00u + threadIdx.x, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_SYSTEM);
+        report_host(pt, 0xD00u + threadIdx.x);
+      }
+    }
+  }
+  __syncthreads();
+
+  using R = Row16<DT>;
+  constexpr int U = 2;
+  const int lane = threadIdx.x & 63;
+  const int gw = blockIdx.x * kWaves + (threadIdx.x >> 6), nw = gridDim.x * kWaves;
+  const uint32_t nv = m.row_bytes / 16;
+  const bool scaled = m.weights != nullptr;
+  for (int t = gw; t < m.T; t += nw) {
+    Rsrc src[kMoeMaxTopK], dst[kMoeMaxTopK];
+    bool on[kMoeMaxTopK];
+    float w[kMoeMaxTopK], dot[kMoeMaxTopK];
+#pragma unroll
+    for (int k = 0; k < kMoeMaxTopK; ++k) {
+      on[k] = false;
+      w[k] = 1.0f;
+      dot[k] = 0.0f;
+      if (k < K) {
+        const int64_t f = (int64_t)t * K + k;
+        const int row = uni(m.row_of[f]);
+        const int e = uni(m.idx[f]);
+        on[k] = row >= 0 && e >= 0 && e < E;
+        if (on[k]) {
+          const uint64_t off = (uint64_t)row * m.row_bytes;
+          dst[k] = make_rsrc(uniform_ptr(s_dy[e / El] + off), m.row_bytes);
+          if (PULL) src[k] = make_rsrc(uniform_ptr(s_y[e / El] + off), m.row_bytes);
+          if (scaled) w[k] = __uint_as_float((uint32_t)uni((int)__float_as_uint(m.weights[f])));
+        }
+      }
+    }
+    const u32x4* g = reinterpret_cast<const u32x4*>(a.in + (uint64_t)t * m.row_bytes);
+    for (uint32_t v0 = lane; v0 < nv; v0 += 64 * U) {
+      u32x4 d[U];
+      u32x4 y[U][kMoeMaxTopK];
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+        if (v0 + u * 64 < nv) d[u] = g[v0 + u * 64];
+      if (PULL) {
+        // every slot's (peer) load in flight before the first use
+#pragma unroll
+        for (int k = 0; k < kMoeMaxTopK; ++k) {
+          if (on[k]) {
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+              if (v0 + u * 64 < nv) y[u][k] = ld16(src[k], (v0 + u * 64) * 16);
+          }
+        }
+      }
+      // push: dy row = w * dout[t], one fp32 multiply and one rounding (a copy without weights)
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        if (v0 + u * 64 < nv) {
+          float dv[R::N];
+          R::unpack(d[u], dv);
+#pragma unroll
+          for (int k = 0; k < kMoeMaxTopK; ++k) {
+            if (on[k]) {
+              u32x4 o = d[u];
+              if (scaled) {
+                float sv[R::N];
+#pragma unroll
+                for (int i = 0; i < R::N; ++i) sv[i] = w[k] * dv[i];
+                o = R::pack(sv);
+              }
+              st16(dst[k], (v0 + u * 64) * 16, o);
+            }
+          }
+          if (PULL) {
+            // pull: per-lane fp32 dot in vector order
+#pragma unroll
+            for (int k = 0; k < kMoeMaxTopK; ++k) {
+              if (on[k]) {
+                float yv[R::N];
+                R::unpack(y[u][k], yv);
+#pragma unroll
+                for (int i = 0; i < R::N; ++i) dot[k] = __builtin_fmaf(dv[i], yv[i], dot[k]);
+              }
+            }
+          }
+        }
+      }
+    }
+    if (PULL) {
+#pragma unroll
+      for (int k = 0; k < kMoeMaxTopK; ++k) {
+        if (k < K) {
+          const float s = on[k] ? wave_sum(dot[k]) : 0.0f;
+          if (lane == 0) m.dweights[(int64_t)t * K + k] = s;
+        }
+      }
+    }
+  }
+  if (!sync_phase(a, 3, e0)) return;
+  finish(a, e0);
+}
+
 }  // namespace
 
 void launch_moe_route(const MoEArgs& m, hipStream_t s) {
@@ -316,6 +459,21 @@ void launch_moe_combine(const MoEArgs& m, int grid, hipStream_t s) {
     case DT_BF16: hipLaunchKernelGGL(k_moe_combine<DT_BF16>, dim3(grid), dim3(kThreads), 0, s, m); break;
     case DT_F16: hipLaunchKernelGGL(k_moe_combine<DT_F16>, dim3(grid), dim3(kThreads), 0, s, m); break;
     default: throw std::invalid_argument("ccmpi: moe_combine supports bf16, fp16 and fp32");
+  }
+}
+
+template <int DT>
+static void launch_moe_combine_bwd_dt(const MoEArgs& m, int grid, hipStream_t s) {
+  if (m.dweights) hipLaunchKernelGGL((k_moe_combine_bwd<DT, true>), dim3(grid), dim3(kThreads), 0, s, m);
+  else hipLaunchKernelGGL((k_moe_combine_bwd<DT, false>), dim3(grid), dim3(kThreads), 0, s, m);
+}
+
+void launch_moe_combine_bwd(const MoEArgs& m, int grid, hipStream_t s) {
+  switch (m.dtype) {
+    case DT_F32: launch_moe_combine_bwd_dt<DT_F32>(m, grid, s); break;
+    case DT_BF16: launch_moe_combine_bwd_dt<DT_BF16>(m, grid, s); break;
+    case DT_F16: launch_moe_combine_bwd_dt<DT_F16>(m, grid, s); break;
+    default: throw std::invalid_argument("ccmpi: moe_combine_backward supports bf16, fp16 and fp32");
   }
 }
 

@@ -1,5 +1,5 @@
 // Host-visible interface of the routed MoE token dispatch / weighted combine
-// kernels (moe.hip).
+// kernels and the combine's backward (moe.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -18,10 +18,12 @@ constexpr int kMoeChunk = 1024;      // (token, slot) entries per routing chunk
 struct MoEArgs {
   CollArgs a;              // dispatch: src_code = scratch (count rows), res_code = recv_x, in = x
                            // combine:  src_code = y, out = out
+                           // combine backward: src_code = y (0: no dweights), res_code = dy, in = dout
   const int32_t* idx;      // [T * K] expert of each entry, -1 = dropped
   int32_t* row_of;         // [T * K] routing: stable rank among this rank's entries of the same expert;
                            //         dispatch: the row taken in the destination's buffer (in place); -1 = none
   const float* weights;    // combine: [T * K] or null (all ones)
+  float* dweights;         // combine backward out: [T * K] <dout[t], y row>, or null (no pull)
   int64_t* expert_counts;  // dispatch out: [E / p] rows per local expert
   int32_t* chunk_hist;     // routing workspace: [chunks][E]
   int32_t* count_row;      // routing out: this rank's staged row at the start of its scratch segment (E int32)
@@ -37,6 +39,7 @@ inline int moe_chunks(int64_t entries) { return (int)((entries + kMoeChunk - 1) 
 void launch_moe_route(const MoEArgs& m, hipStream_t s);
 void launch_moe_dispatch(const MoEArgs& m, int grid, hipStream_t s);
 void launch_moe_combine(const MoEArgs& m, int grid, hipStream_t s);
+void launch_moe_combine_bwd(const MoEArgs& m, int grid, hipStream_t s);
 
 }  // namespace dev
 }  // namespace ccmpi

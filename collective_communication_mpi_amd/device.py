@@ -191,6 +191,32 @@ def moe_validate(p: int, x, topk_idx, num_experts: int, recv_x) -> Tuple[int, in
     return int(T), int(K), int(D)
 
 
+def moe_backward_validate(handle, dout, weights=None, y=None, dy=None) -> None:
+    """Argument rules of ``moe_combine_backward`` that need no GPU (shapes and dtypes
+    against the dispatch's handle); raises ValueError.  ``weights``, ``y`` and ``dy`` may
+    be None (all ones / no ``dweights`` / allocated by the call); ``y`` and ``dy`` must not overlap."""
+    import torch
+
+    h = handle
+    if dout.dim() != 2 or tuple(dout.shape) != (h.T, h.D):
+        raise ValueError(f"moe_combine_backward: dout must be [T, D] = [{h.T}, {h.D}], got {tuple(dout.shape)}")
+    if dout.dtype != h.dtype:
+        raise ValueError(f"moe_combine_backward: dout must have the dispatch's dtype {h.dtype}, got {dout.dtype}")
+    if weights is not None and (weights.dtype != torch.float32 or tuple(weights.shape) != (h.T, h.K)):
+        raise ValueError("moe_combine_backward: weights must be [T, K] fp32")
+    for name, t in (("y", y), ("dy", dy)):
+        if t is None:
+            continue
+        if t.dim() != 2 or t.shape[1] != h.D or t.dtype != h.dtype:
+            raise ValueError(f"moe_combine_backward: {name} must be [cap, D] with the dispatch's dtype and row length")
+        if t.shape[0] < h.cap:
+            raise ValueError(f"moe_combine_backward: {name} has {t.shape[0]} rows, the dispatch buffer had {h.cap}")
+    if y is not None and dy is not None:
+        y0, d0 = y.data_ptr(), dy.data_ptr()
+        if y0 < d0 + dy.numel() * dy.element_size() and d0 < y0 + y.numel() * y.element_size():
+            raise ValueError("moe_combine_backward: y and dy must not overlap (peers write dy while y is read)")
+
+
 class MoEHandle:
     """What ``moe_dispatch`` leaves for ``moe_combine``: device tensors only.
 
@@ -1276,6 +1302,49 @@ class DeviceGroup:
                             0 if weights is None else weights.data_ptr(), h.T, h.K, h.num_experts,
                             h.D * y.element_size(), dtype_code(h.dtype), s, self._budget(max_blocks))
         return out
+
+    @trace_call("moe_combine_backward")
+    def moe_combine_backward(self, dout, handle: MoEHandle, weights=None, y=None, dy=None,
+                             max_blocks: Optional[int] = None):
+        """Backward of :meth:`moe_combine` in one kernel (``k_moe_combine_bwd``): ``dout``
+        [T, D] (the handle's dtype, 16-B aligned) gives, in the owner's ``dy`` (symmetric
+        heap, at least ``cap`` rows; allocated if None),
+        ``dy_owner[row_of[t,k]] = w[t,k] * dout[t]`` -- one fp32 multiply, rounded once; with
+        ``weights=None`` a bitwise copy -- and, when the forward's ``y`` [cap, D] (symmetric
+        heap) is given, ``dweights[t,k] = <dout[t], y_owner[row_of[t,k]]>`` [T, K] fp32 (0 for
+        a slot that was dropped or refused; bitwise reproducible).  Without ``y`` nothing is
+        pulled and ``dweights`` is None; ``y`` is given on every rank or on none (a rank that
+        pulls reads the ``y`` of every owner; with an owner that has none the call fails:
+        ``check()`` raises, fault code 0xD00 + owner).  Every routed row of ``dy`` is written
+        exactly once; rows at or past the rank's total are left untouched.  A collective:
+        every rank calls it, also with T = 0.  No atomics, no [T * K, D] staging, no host synchronisation.
+        Returns ``(dy, dweights)``."""
+        h = handle
+        moe_backward_validate(h, dout, weights, y, dy)
+        torch = self.torch
+        self._check(dout, "dout")
+        if dout.data_ptr() % 16:
+            raise ValueError("moe_combine_backward: dout must be 16-B aligned")
+        if weights is not None:
+            self._check(weights, "weights")
+        if y is not None:
+            self._check(y, "y")
+            if y.data_ptr() % 16 or not self.is_symmetric(y):
+                raise ValueError("moe_combine_backward: y must come from the symmetric heap (comm.empty)")
+        if dy is None:
+            dy = self.empty((h.cap, h.D), h.dtype)
+        else:
+            self._check(dy, "dy")
+            if dy.data_ptr() % 16 or not self.is_symmetric(dy):
+                raise ValueError("moe_combine_backward: dy must come from the symmetric heap (comm.empty)")
+        dweights = None if y is None else torch.empty((h.T, h.K), dtype=torch.float32, device=self.device)
+        s = self._stream()
+        self.dc.moe_combine_bwd(dout.data_ptr(), 0 if y is None else y.data_ptr(), 0 if y is None else y.shape[0],
+                                dy.data_ptr(), dy.shape[0], 0 if y is None else dweights.data_ptr(),
+                                h.topk_idx.data_ptr(), h.row_of.data_ptr(),
+                                0 if weights is None else weights.data_ptr(), h.T, h.K, h.num_experts,
+                                h.D * dout.element_size(), dtype_code(h.dtype), s, self._budget(max_blocks))
+        return dy, dweights
 
     @trace_call("bcast")
     def bcast(self, buf, root: int = 0, algo: str = "auto"):

@@ -21,3 +21,4 @@ from .tensor_parallel import (  # noqa: F401,E402
     scatter_to_tensor_parallel_region,
 )
 from .moe_experts import GroupedExpertsMLP  # noqa: F401,E402
+from .moe import RoutedMoE, moe_combine, moe_dispatch  # noqa: F401,E402
