@@ -223,15 +223,17 @@ class Communicator(object):
         else:
             self.comm.Alltoallv([src_array, list(send_counts)], [dest_array, list(recv_counts)])
 
-    def moe_dispatch(self, x, topk_idx, num_experts: int, recv_x, max_blocks=None):
+    def moe_dispatch(self, x, topk_idx, num_experts: int, recv_x, max_blocks=None, *, expert_capacity=None):
         """Routed MoE token dispatch of CUDA tensors (``DeviceGroup.moe_dispatch``): ``x``
         [T, D] and the router's ``topk_idx`` [T, K] go in, ``recv_x`` (from ``comm.empty``)
         receives the rows of this rank's experts grouped by expert.  Returns the handle
-        ``moe_combine`` takes.  ``total_bytes_transferred`` is not advanced: the counts
+        ``moe_combine`` takes.  ``expert_capacity`` (the same on every rank) keeps at most
+        that many rows per expert and drops the rest without an error
+        (``handle.num_dropped``).  ``total_bytes_transferred`` is not advanced: the counts
         never reach the host."""
         if not _is_device(x):
             raise TypeError("moe_dispatch runs on the device plane: x must be a CUDA tensor")
-        return self.dev.moe_dispatch(x, topk_idx, num_experts, recv_x, max_blocks)
+        return self.dev.moe_dispatch(x, topk_idx, num_experts, recv_x, max_blocks, expert_capacity=expert_capacity)
 
     def moe_combine(self, y, handle, weights=None, out=None, max_blocks=None):
         """Weighted combine of the expert outputs ``y`` back onto the source tokens

@@ -778,8 +778,14 @@ static void moe_check_shape(int size, int64_t T, int K, int E, uint64_t row_byte
 
 void DeviceComm::moe_dispatch(uint64_t x, uint64_t idx, uint64_t recv_x, uint64_t recv_rows, uint64_t row_of,
                               uint64_t expert_counts, uint64_t chunk_hist, int64_t T, int K, int E,
-                              uint64_t row_bytes, uint64_t stream, int max_blocks) {
+                              uint64_t row_bytes, uint64_t stream, int max_blocks, int64_t expert_cap,
+                              uint64_t num_dropped) {
   moe_check_shape(size_, T, K, E, row_bytes);
+  if (expert_cap < 0 || expert_cap >= (1ll << 31))
+    throw std::invalid_argument("ccmpi: moe_dispatch needs 0 <= expert capacity < 2^31");
+  if (expert_cap > 0 && (uint64_t)(E / size_) * (uint64_t)expert_cap > recv_rows)
+    throw std::invalid_argument("ccmpi: moe_dispatch needs (E / p) * expert capacity rows of recv_x");
+  if (num_dropped % 8) throw std::invalid_argument("ccmpi: moe_dispatch num_dropped must be 8-B aligned");
   if (x % 16 || recv_x % 16) throw std::invalid_argument("ccmpi: moe_dispatch buffers must be 16-B aligned");
   if (recv_rows < 1 || recv_rows >= (1ull << 31))
     throw std::invalid_argument("ccmpi: moe_dispatch needs 1 <= rows of recv_x < 2^31");
@@ -805,6 +811,8 @@ void DeviceComm::moe_dispatch(uint64_t x, uint64_t idx, uint64_t recv_x, uint64_
   m.El = E / size_;
   m.row_bytes = (uint32_t)row_bytes;
   m.cap = (int32_t)recv_rows;
+  m.expert_cap = (int32_t)expert_cap;
+  m.num_dropped = reinterpret_cast<int64_t*>(num_dropped);
   launch_moe_route(m, st);
   launch_moe_dispatch(m, std::max(1, std::min(max_blocks > 0 ? max_blocks : 256, kMaxBlocks)), st);
 }

@@ -101,9 +101,14 @@ class DeviceComm {
   // order.  Outputs, all on the device: row_of [T, K] int32 (row taken, -1 = none),
   // expert_counts [E / p] int64.  chunk_hist: int32 workspace of moe_chunks(T * K) * E.
   // A row past the owner's capacity is not written (fault code 0xA00 + owner).
+  // expert_cap (0: none; the same value on every rank): every expert keeps its first expert_cap
+  // entries in (source rank, token, slot) order, the others are dropped (row_of = -1, not
+  // written, no fault code); expert_counts counts the kept rows and recv_x needs
+  // (E / p) * expert_cap rows.  num_dropped: [1] int64 on the device (0: not wanted), this
+  // rank's dropped entries.
   void moe_dispatch(uint64_t x, uint64_t idx, uint64_t recv_x, uint64_t recv_rows, uint64_t row_of,
                     uint64_t expert_counts, uint64_t chunk_hist, int64_t T, int K, int E, uint64_t row_bytes,
-                    uint64_t stream, int max_blocks);
+                    uint64_t stream, int max_blocks, int64_t expert_cap, uint64_t num_dropped);
   // Weighted combine (pull): out[t] = sum_k w[t, k] * y_owner(idx[t, k])[row_of[t, k]], fp32 in
   // slot order, rounded once.  y [y_rows, row_bytes] registered on every rank; weights
   // [T, K] fp32 or 0 (all ones); out local.

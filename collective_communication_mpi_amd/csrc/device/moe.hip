@@ -21,6 +21,13 @@
 //                          (local expert, source rank, token, slot) order whatever the
 //                          scheduling.  A row past the owner's capacity is not written
 //                          (fault code 0xA00 + owner, row_of = -1).
+//                          With an expert capacity Ce (MoEArgs::expert_cap, rank-invariant)
+//                          expert e keeps its first Ce entries in that order: entry pos of
+//                          this rank is kept iff before(e) + pos < Ce, the expert has
+//                          col'(e) = min(col(e), Ce) rows and base uses col'.  All of it is
+//                          closed-form from the count matrix in LDS: no exchange, no atomics.
+//                          A dropped entry gets row_of = -1, is not written and records no
+//                          fault; CTA 0 writes this rank's number of them to num_dropped.
 //   combine  (collective)  k_moe_combine: the start barrier publishes y; one wave per
 //                          token issues the loads of its K rows (peer memory) before
 //                          the fp32 multiply-add chain in slot order, rounds once and
@@ -123,10 +130,12 @@ __global__ void __launch_bounds__(kThreads) k_moe_dispatch(MoEArgs m) {
   __shared__ int32_t C[kMaxRanks * kMoeMaxExperts];  // C[i * E + e]: rank i's entries for expert e
   __shared__ int32_t s_col[kMoeMaxExperts], s_before[kMoeMaxExperts], s_base[kMoeMaxExperts];
   __shared__ int32_t s_cap[kMaxRanks];
+  __shared__ int32_t s_drop[kMoeMaxExperts];  // this rank's entries of expert e over the expert capacity
   __shared__ char* s_out[kMaxRanks];
   const CollArgs& a = m.a;
   const PeerTable* pt = a.pt;
   const int E = m.E, El = m.El, K = m.K;
+  const int Ce = m.expert_cap;  // rows kept per expert, 0 = no limit
   if (threadIdx.x == 0) {  // published with the start barrier (thread 0 releases before its flag)
     int32_t* mine = reinterpret_cast<int32_t*>(resolve(pt, pt->rank, a.src_code));
     __hip_atomic_store(mine + E, m.cap, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -150,8 +159,15 @@ __global__ void __launch_bounds__(kThreads) k_moe_dispatch(MoEArgs m) {
       col += v;
       if (i < me) before += v;
     }
+    if (Ce > 0) {
+      // an expert keeps its first Ce entries in (source rank, token, slot) order: this rank's
+      // entry pos is kept iff before + pos < Ce, so it keeps clamp(Ce - before, 0, C[me][e])
+      const int mine = C[me * E + threadIdx.x];
+      s_drop[threadIdx.x] = mine - min(max(Ce - before, 0), mine);
+      col = min(col, Ce);
+    }
     s_col[threadIdx.x] = col;
-    s_before[threadIdx.x] = before;
+    s_before[threadIdx.x] = before;  // not clamped: only read for kept entries, where before < Ce
   }
   __syncthreads();
   if (threadIdx.x < E) {
@@ -160,6 +176,14 @@ __global__ void __launch_bounds__(kThreads) k_moe_dispatch(MoEArgs m) {
     s_base[threadIdx.x] = b;
   }
   if (blockIdx.x == 0 && threadIdx.x < El) m.expert_counts[threadIdx.x] = s_col[me * El + threadIdx.x];
+  if (blockIdx.x == 0 && threadIdx.x < 64 && m.num_dropped) {  // wave 0: a fixed butterfly, no atomics
+    int d = 0;
+    if (Ce > 0)
+      for (int ee = threadIdx.x; ee < E; ee += 64) d += s_drop[ee];
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) d += __shfl_xor(d, s, 64);
+    if (threadIdx.x == 0) *m.num_dropped = d;
+  }
   __syncthreads();
 
   const int lane = threadIdx.x & 63;
@@ -178,10 +202,11 @@ __global__ void __launch_bounds__(kThreads) k_moe_dispatch(MoEArgs m) {
           const int e = uni(m.idx[f]);
           const int owner = e / El;
           const int row = uni(s_base[e]) + pos;
-          on[k] = row < uni(s_cap[owner]);
+          const bool kept = Ce <= 0 || uni(s_before[e]) + pos < Ce;  // over the expert capacity: dropped, no fault
+          on[k] = kept && row < uni(s_cap[owner]);
           if (on[k]) {
             dst[k] = make_rsrc(uniform_ptr(s_out[owner] + (uint64_t)row * m.row_bytes), m.row_bytes);
-          } else if (lane == 0) {
+          } else if (kept && lane == 0) {
             __hip_atomic_store(&pt->sig[me]->error, 0xA00u + owner, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             report_host(pt, 0xA00u + owner);
           }

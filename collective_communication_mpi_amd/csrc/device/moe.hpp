@@ -31,6 +31,8 @@ struct MoEArgs {
   uint32_t row_bytes;      // D * element size, a 16-B multiple
   int32_t cap;             // rows of this rank's recv_x
   int32_t dtype;           // combine: DT_F32 / DT_BF16 / DT_F16
+  int32_t expert_cap;      // dispatch: rows kept per expert (the same on every rank), 0 = no limit
+  int64_t* num_dropped;    // dispatch out: [1] this rank's entries over expert_cap, or null
 };
 
 inline int moe_chunks(int64_t entries) { return (int)((entries + kMoeChunk - 1) / kMoeChunk); }

@@ -131,7 +131,7 @@ MOE_MAX_TOPK = 8
 _MOE_CHUNK = 1024  # entries per routing chunk (csrc/device/moe.hpp kMoeChunk)
 
 
-def moe_layout(counts, me: int):
+def moe_layout(counts, me: int, expert_capacity: Optional[int] = None):
     """Row layout of the routed MoE dispatch from the p x E count matrix
     (``counts[i][e]`` = (token, slot) entries of rank i routed to expert e; expert e
     lives on rank ``e // (E // p)``).  Every rank's receive buffer is ordered by
@@ -139,7 +139,12 @@ def moe_layout(counts, me: int):
     expert e form one segment.  Returns ``(base, expert_counts, totals)``:
     ``base[i][e]`` = first row of that segment in the owner's buffer (p x E, the
     segments of all ranks), ``expert_counts`` = rows per local expert of rank ``me``
-    (E // p), ``totals[j]`` = valid rows on rank j (p)."""
+    (E // p), ``totals[j]`` = valid rows on rank j (p).
+
+    With ``expert_capacity`` Ce every expert keeps its first Ce entries in that order (see
+    ``moe_kept``): an expert has ``min(col, Ce)`` rows, the kept rows of source i start at
+    ``min(before, Ce)`` within the expert (for a source that keeps nothing this is where its
+    empty segment lies), and the counts and totals are those of the kept rows."""
     c = np.asarray(counts, dtype=np.int64)
     if c.ndim != 2 or c.shape[0] < 1 or c.shape[1] % c.shape[0]:
         raise ValueError("moe_layout: counts must be a p x E matrix with E a multiple of p")
@@ -150,17 +155,44 @@ def moe_layout(counts, me: int):
         raise ValueError("moe_layout: rank out of range")
     El = E // p
     col = c.sum(axis=0)                                  # rows of each expert
+    before = np.cumsum(c, axis=0) - c                    # rows of sources < i for expert e
+    if expert_capacity is not None:
+        Ce = _expert_capacity(expert_capacity)
+        col = np.minimum(col, Ce)
+        before = np.minimum(before, Ce)
     per_rank = col.reshape(p, El)
     first = (np.cumsum(per_rank, axis=1) - per_rank).reshape(E)  # first row of expert e on its rank
-    before = np.cumsum(c, axis=0) - c                    # rows of sources < i for expert e
     base = first[None, :] + before
     return base, col[me * El:(me + 1) * El].copy(), per_rank.sum(axis=1)
 
 
-def moe_validate(p: int, x, topk_idx, num_experts: int, recv_x) -> Tuple[int, int, int]:
+def _expert_capacity(expert_capacity) -> int:
+    Ce = int(expert_capacity)
+    if Ce < 1:
+        raise ValueError(f"moe: expert_capacity must be at least 1, got {Ce}")
+    return Ce
+
+
+def moe_kept(counts, expert_capacity: int):
+    """The p x E matrix of entries that survive a per-expert capacity Ce: the entries of
+    expert e are ranked by (source rank, source token, slot), the order their rows have, and
+    the first Ce are kept, so ``kept[i][e] = clamp(Ce - before_i[e], 0, counts[i][e])`` with
+    ``before_i[e] = sum_{i' < i} counts[i'][e]``.  ``counts - kept`` is what each rank drops
+    (its ``MoEHandle.num_dropped`` is the sum of its row)."""
+    c = np.asarray(counts, dtype=np.int64)
+    if c.ndim != 2 or c.shape[0] < 1 or (c < 0).any():
+        raise ValueError("moe_kept: counts must be a non-negative p x E matrix")
+    Ce = _expert_capacity(expert_capacity)
+    before = np.cumsum(c, axis=0) - c
+    return np.clip(Ce - before, 0, c)
+
+
+def moe_validate(p: int, x, topk_idx, num_experts: int, recv_x,
+                 expert_capacity: Optional[int] = None) -> Tuple[int, int, int]:
     """Argument rules of ``moe_dispatch`` that need no GPU (shapes, dtypes, bounds);
     raises ValueError, returns (T, K, D).  They depend on rank-invariant properties
-    only, so every rank raises together."""
+    only, so every rank raises together.  With ``expert_capacity`` Ce (>= 1) ``recv_x``
+    needs ``(E / p) * Ce`` rows: then no kept row can fall past the buffer."""
     import torch
 
     E = int(num_experts)
@@ -188,6 +220,13 @@ def moe_validate(p: int, x, topk_idx, num_experts: int, recv_x) -> Tuple[int, in
         raise ValueError("moe_dispatch: recv_x needs at least one row")
     if T * K >= 1 << 31:
         raise ValueError("moe_dispatch: T * K must be below 2^31")
+    if expert_capacity is not None:
+        Ce = int(expert_capacity)
+        if Ce < 1:
+            raise ValueError(f"moe_dispatch: expert_capacity must be at least 1, got {Ce}")
+        if recv_x.shape[0] < (E // p) * Ce:
+            raise ValueError(f"moe_dispatch: recv_x has {recv_x.shape[0]} rows, expert_capacity {Ce} needs "
+                             f"(E / p) * expert_capacity = {(E // p) * Ce}")
     return int(T), int(K), int(D)
 
 
@@ -221,14 +260,19 @@ class MoEHandle:
     """What ``moe_dispatch`` leaves for ``moe_combine``: device tensors only.
 
     ``row_of`` [T, K] int32: the row each (token, slot) took in its expert's rank's
-    buffer (-1: dropped, or refused for lack of capacity); ``topk_idx`` [T, K] as
-    int32; ``expert_counts`` [E // p] int64: rows per local expert on this rank."""
+    buffer (-1: dropped by the router, dropped over ``expert_capacity``, or refused for
+    lack of buffer rows); ``topk_idx`` [T, K] as int32; ``expert_counts`` [E // p] int64:
+    rows per local expert on this rank; ``num_dropped`` [1] int64: this rank's routed entries
+    that went over ``expert_capacity`` (0 without one); ``expert_capacity``: the dispatch's."""
 
-    __slots__ = ("row_of", "topk_idx", "expert_counts", "num_experts", "T", "K", "D", "dtype", "cap")
+    __slots__ = ("row_of", "topk_idx", "expert_counts", "num_experts", "T", "K", "D", "dtype", "cap",
+                 "num_dropped", "expert_capacity")
 
-    def __init__(self, row_of, topk_idx, expert_counts, num_experts, T, K, D, dtype, cap) -> None:
+    def __init__(self, row_of, topk_idx, expert_counts, num_experts, T, K, D, dtype, cap,
+                 num_dropped=None, expert_capacity=None) -> None:
         self.row_of, self.topk_idx, self.expert_counts = row_of, topk_idx, expert_counts
         self.num_experts, self.T, self.K, self.D, self.dtype, self.cap = num_experts, T, K, D, dtype, cap
+        self.num_dropped, self.expert_capacity = num_dropped, expert_capacity
 
 
 def stale_keys(keys, key) -> List[tuple]:
@@ -1231,7 +1275,8 @@ class DeviceGroup:
         return dst
 
     @trace_call("moe_dispatch")
-    def moe_dispatch(self, x, topk_idx, num_experts: int, recv_x, max_blocks: Optional[int] = None) -> MoEHandle:
+    def moe_dispatch(self, x, topk_idx, num_experts: int, recv_x, max_blocks: Optional[int] = None, *,
+                     expert_capacity: Optional[int] = None) -> MoEHandle:
         """Routed MoE token dispatch: the router's output goes in, expert-grouped rows
         come out.  ``num_experts`` E (<= 256, a multiple of p) experts, E // p consecutive
         ones per rank (expert e lives on rank ``e // (E // p)``).  ``x`` [T, D] (bf16 /
@@ -1246,9 +1291,20 @@ class DeviceGroup:
         (``k_moe_dispatch``): no host synchronisation, capturable in a HIP graph.
         Returns a :class:`MoEHandle` (``row_of``, ``expert_counts``, ...).  A row that
         would land at or past ``cap`` is not written, its ``row_of`` stays -1 and
-        ``check()`` raises on the sender (fault code 0xA00 + owner)."""
+        ``check()`` raises on the sender (fault code 0xA00 + owner).
+
+        ``expert_capacity`` Ce (the same value on every rank; ``None``: no limit) caps every
+        expert at Ce rows.  The entries of an expert are ranked by (source rank, source
+        token, slot), the order their rows have, and the first Ce are kept; an entry over
+        capacity is dropped: ``row_of`` -1, nothing written, no fault code, so the combine
+        adds nothing for it and its gradients are zero.  The kept rows keep the order above
+        and ``expert_counts`` counts them; ``handle.num_dropped`` ([1] int64 on the device)
+        is the number of this rank's entries dropped.  ``recv_x`` needs ``(E / p) * Ce``
+        rows, a bound known on the host, and then the ``cap`` refusal cannot fire.  The
+        decision is closed-form from the count matrix every CTA already holds (``moe_kept``
+        / ``moe_layout`` are its host mirrors): no extra exchange, no atomics."""
         torch = self.torch
-        T, K, D = moe_validate(self.size, x, topk_idx, num_experts, recv_x)
+        T, K, D = moe_validate(self.size, x, topk_idx, num_experts, recv_x, expert_capacity)
         self._check(x, "x")
         self._check(topk_idx, "topk_idx")
         self._check(recv_x, "recv_x")
@@ -1262,11 +1318,13 @@ class DeviceGroup:
         expert_counts = torch.empty(E // self.size, dtype=torch.int64, device=self.device)
         chunks = (T * K + _MOE_CHUNK - 1) // _MOE_CHUNK
         hist = torch.empty(max(1, chunks * E), dtype=torch.int32, device=self.device)
+        num_dropped = torch.empty(1, dtype=torch.int64, device=self.device)
+        Ce = None if expert_capacity is None else int(expert_capacity)
         s = self._stream()
         self.dc.moe_dispatch(x.data_ptr(), idx.data_ptr(), recv_x.data_ptr(), recv_x.shape[0], row_of.data_ptr(),
                              expert_counts.data_ptr(), hist.data_ptr(), T, K, E, D * x.element_size(), s,
-                             self._budget(max_blocks))
-        return MoEHandle(row_of, idx, expert_counts, E, T, K, D, x.dtype, int(recv_x.shape[0]))
+                             self._budget(max_blocks), Ce or 0, num_dropped.data_ptr())
+        return MoEHandle(row_of, idx, expert_counts, E, T, K, D, x.dtype, int(recv_x.shape[0]), num_dropped, Ce)
 
     @trace_call("moe_combine")
     def moe_combine(self, y, handle: MoEHandle, weights=None, out=None, max_blocks: Optional[int] = None):

@@ -19,4 +19,8 @@ from .kernels import (  # noqa: F401
     grouped_linear,
     grouped_validate,
     grouped_tile_map,
+    moe_gate,
+    moe_gate_forward,
+    moe_gate_backward,
+    moe_gate_validate,
 )

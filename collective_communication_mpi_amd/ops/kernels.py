@@ -501,3 +501,111 @@ def grouped_linear(x: torch.Tensor, w: torch.Tensor, counts: torch.Tensor) -> to
     if w.dtype not in (torch.bfloat16, torch.float32):
         raise TypeError("grouped_linear weights must be bf16 or fp32")
     return _GroupedLinear.apply(x, w, counts)
+
+
+# ---------------------------------------------------------------------------
+# fused top-k router (csrc/device/moe_gate.hip)
+# ---------------------------------------------------------------------------
+MOE_GATE_MAX_EXPERTS = 256  # = device.MOE_MAX_EXPERTS
+MOE_GATE_MAX_TOPK = 8       # = device.MOE_MAX_TOPK
+MOE_GATE_CHUNK = 64         # tokens per CTA (csrc/device/moe_gate.hpp kGateChunk): fixes prob_sum's summation order
+
+
+def moe_gate_validate(logits, top_k: int):
+    """Argument rules of ``moe_gate`` that need no GPU; raises TypeError (dtypes) / ValueError
+    (shapes, bounds) and returns ``(T, E, K)``: ``logits`` [T, E] fp32 and contiguous,
+    ``1 <= E <= 256``, ``1 <= top_k <= min(8, E)``, ``T >= 0``."""
+    if logits.dtype != torch.float32:
+        raise TypeError(f"moe_gate expects fp32 logits, got {logits.dtype}")
+    if logits.dim() != 2:
+        raise ValueError(f"moe_gate: logits must be [T, E], got {tuple(logits.shape)}")
+    T, E = logits.shape
+    K = int(top_k)
+    if E < 1 or E > MOE_GATE_MAX_EXPERTS:
+        raise ValueError(f"moe_gate: the number of experts must be in [1, {MOE_GATE_MAX_EXPERTS}], got {E}")
+    if K < 1 or K > min(MOE_GATE_MAX_TOPK, E):
+        raise ValueError(f"moe_gate: top_k must be in [1, min({MOE_GATE_MAX_TOPK}, E = {E})], got {K}")
+    if not logits.is_contiguous():
+        raise ValueError("moe_gate: logits must be contiguous")
+    if T >= (1 << 31) - MOE_GATE_CHUNK:
+        raise ValueError("moe_gate: T must be below 2^31 - 64")
+    return int(T), int(E), K
+
+
+def moe_gate_forward(logits: torch.Tensor, top_k: int, renormalize: bool = True):
+    """The router in one pass over ``logits`` [T, E] (``k_moe_gate_fwd`` + the partial
+    reduction): returns ``(weights [T, K] fp32, idx [T, K] int32, prob_sum [E] fp32,
+    expert_tokens [E] int64)``, plain tensors, no autograd.  ``idx`` is the first K entries of a
+    stable sort of the row by (-logit, index), in that order; ``weights`` are the softmax
+    probabilities of those experts, divided by their sum when ``renormalize``;
+    ``prob_sum[e] = sum_t p[t, e]``; ``expert_tokens[e]`` counts the (t, k) with ``idx == e``.
+    ``-inf`` logits are legal (probability 0) while every row has a finite one.  No host
+    synchronisation, no atomics: bitwise reproducible and capturable in a graph."""
+    T, E, K = moe_gate_validate(logits, top_k)
+    dev = logits.device
+    chunks = (T + MOE_GATE_CHUNK - 1) // MOE_GATE_CHUNK
+    weights = torch.empty((T, K), dtype=torch.float32, device=dev)
+    idx = torch.empty((T, K), dtype=torch.int32, device=dev)
+    prob_sum = torch.empty(E, dtype=torch.float32, device=dev)
+    expert_tokens = torch.empty(E, dtype=torch.int64, device=dev)
+    part_p = torch.empty((max(chunks, 1), E), dtype=torch.float32, device=dev)
+    part_c = torch.empty((max(chunks, 1), E), dtype=torch.int32, device=dev)
+    _D().moe_gate_fwd(logits.data_ptr(), weights.data_ptr(), idx.data_ptr(), part_p.data_ptr(), part_c.data_ptr(),
+                      prob_sum.data_ptr(), expert_tokens.data_ptr(), T, E, K, bool(renormalize), _stream(logits))
+    return weights, idx, prob_sum, expert_tokens
+
+
+def moe_gate_backward(logits: torch.Tensor, idx: torch.Tensor, dweights: torch.Tensor,
+                      dprob_sum: Optional[torch.Tensor] = None, renormalize: bool = True) -> torch.Tensor:
+    """``dlogits`` [T, E] of ``moe_gate_forward`` (``k_moe_gate_bwd``): the probabilities are
+    recomputed from ``logits``; ``idx`` [T, K] int32 is the forward's, ``dweights`` [T, K] fp32
+    the gradient of its weights, ``dprob_sum`` [E] fp32 that of ``prob_sum`` (None: zero)."""
+    T, E, _ = moe_gate_validate(logits, idx.shape[1] if idx.dim() == 2 else 0)
+    K = idx.shape[1]
+    if idx.dtype != torch.int32 or dweights.dtype != torch.float32:
+        raise TypeError("moe_gate_backward expects int32 idx and fp32 dweights")
+    if tuple(idx.shape) != (T, K) or tuple(dweights.shape) != (T, K) or not idx.is_contiguous() \
+            or not dweights.is_contiguous():
+        raise ValueError("moe_gate_backward: idx and dweights must be contiguous [T, K]")
+    if dprob_sum is not None:
+        if dprob_sum.dtype != torch.float32:
+            raise TypeError("moe_gate_backward expects fp32 dprob_sum")
+        if tuple(dprob_sum.shape) != (E,) or not dprob_sum.is_contiguous():
+            raise ValueError("moe_gate_backward: dprob_sum must be a contiguous [E] tensor")
+    for t in (idx, dweights, dprob_sum):
+        if t is not None and t.device != logits.device:
+            raise ValueError("moe_gate_backward: every tensor must be on the logits' device")
+    dlogits = torch.empty_like(logits)
+    _D().moe_gate_bwd(logits.data_ptr(), idx.data_ptr(), dweights.data_ptr(),
+                      0 if dprob_sum is None else dprob_sum.data_ptr(), dlogits.data_ptr(), T, E, K,
+                      bool(renormalize), _stream(logits))
+    return dlogits
+
+
+class _MoEGate(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, top_k, renormalize):
+        weights, idx, prob_sum, expert_tokens = moe_gate_forward(logits, top_k, renormalize)
+        ctx.save_for_backward(logits, idx)
+        ctx.renormalize = renormalize
+        ctx.mark_non_differentiable(idx, expert_tokens)
+        return weights, idx, prob_sum, expert_tokens
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dweights, _didx, dprob_sum, _dtokens):
+        logits, idx = ctx.saved_tensors
+        dweights = torch.zeros_like(idx, dtype=torch.float32) if dweights is None else dweights.contiguous()
+        if dprob_sum is not None:
+            dprob_sum = dprob_sum.contiguous()
+        return moe_gate_backward(logits, idx, dweights, dprob_sum, ctx.renormalize), None, None
+
+
+def moe_gate(logits: torch.Tensor, top_k: int, renormalize: bool = True):
+    """Differentiable ``moe_gate_forward``: ``(weights, idx, prob_sum, expert_tokens)`` of the
+    router ``logits`` [T, E] fp32, differentiable in ``logits`` through ``weights`` and
+    ``prob_sum`` (one ``k_moe_gate_bwd`` launch, which recomputes the softmax from the saved
+    logits: nothing else of size [T, E] is kept).  ``prob_sum`` and ``expert_tokens`` are the
+    statistics of a load-balancing loss (``RoutedMoE.aux_loss``)."""
+    moe_gate_validate(logits, top_k)
+    return _MoEGate.apply(logits, int(top_k), bool(renormalize))

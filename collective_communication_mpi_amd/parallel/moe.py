@@ -30,6 +30,7 @@ import math
 
 import torch
 
+from .. import ops
 from .moe_experts import GroupedExpertsMLP
 
 
@@ -88,15 +89,19 @@ class _Combine(torch.autograd.Function):
         return dy, dw, None, None
 
 
-def moe_dispatch(group, x, topk_idx, num_experts: int, cap: int):
+def moe_dispatch(group, x, topk_idx, num_experts: int, cap: int, *, expert_capacity=None):
     """Differentiable ``group.moe_dispatch``: ``x`` [T, D] and ``topk_idx`` [T, K] give
     ``(recv_x, handle)``, ``recv_x`` [cap, D] allocated from the symmetric heap.
     Differentiable in ``x``; the backward stages the gradient of ``recv_x`` into the heap
     when needed and runs the unweighted ``moe_combine`` (a collective: see the module
-    notes).  Rows of the gradient at or past the rank's total are never read."""
+    notes).  Rows of the gradient at or past the rank's total are never read.
+    ``expert_capacity`` (the same on every rank) is the dispatch's: an entry over its
+    expert's capacity is dropped (``row_of`` -1, counted in ``handle.num_dropped``), takes no
+    row and gets no gradient."""
     dev = _dev(group)
     recv_x = dev.empty((int(cap), x.shape[1]), x.dtype)
-    handle = dev.moe_dispatch(_aligned(x.detach()), topk_idx, int(num_experts), recv_x)
+    handle = dev.moe_dispatch(_aligned(x.detach()), topk_idx, int(num_experts), recv_x,
+                              expert_capacity=expert_capacity)
     return _Dispatch.apply(x, recv_x, dev, handle), handle
 
 
@@ -117,17 +122,37 @@ class RoutedMoE(torch.nn.Module):
 
     ``forward(x)`` with this rank's tokens ``x`` [T, d_model] in bf16, the grouped GEMMs'
     input type (T may differ per rank and be 0): router logits ``x . router^T`` in fp32,
-    softmax and ``topk`` in torch (they are [T, E]-sized), the chosen probabilities renormalised to sum to one per token
+    softmax and ``topk`` in torch (they are [T, E]-sized; ``gate="fused"``: one kernel), the chosen probabilities renormalised to sum to one per token
     (``renormalize``), then ``moe_dispatch -> GroupedExpertsMLP -> moe_combine``.  Gradients
     reach the router through the combine's ``dweights``, and ``x`` through both the
     dispatch backward and the router.  ``capacity`` is the number of rows of every rank's
     receive buffer: a host-known bound on the rows one rank can receive (at most
     ``top_k`` times all ranks' tokens).  ``last_handle`` is the most recent forward's
     ``MoEHandle`` (``topk_idx``, ``row_of``, ``expert_counts``).  Forward and backward are
-    collectives: every rank runs both."""
+    collectives: every rank runs both.
+
+    ``expert_capacity`` (None: no limit; the same on every rank) caps the rows of every
+    expert: the first ``expert_capacity`` entries of an expert in (source rank, token, slot)
+    order are kept, the others dropped without an error -- they add nothing to the output
+    and get no gradient; the weights of a token's kept slots are not renormalised again.
+    ``last_handle.num_dropped`` counts this rank's dropped entries.  ``capacity`` must then be
+    at least ``(num_experts / p) * expert_capacity``, which is also all it needs to be:
+    ``capacity_for`` gives the usual ``factor * tokens * top_k / num_experts``.
+
+    ``gate="fused"`` computes the same logits and hands them to ``ops.moe_gate`` (softmax,
+    top-k, renormalisation and the statistics below in one kernel, one more for the
+    backward); ``gate="torch"`` is the chain of torch ops.  The two agree up to fp32 rounding,
+    and on ties between logits the fused gate takes the lower expert index.
+
+    After a forward ``aux_loss`` is the Switch load-balancing loss of this rank's tokens,
+    ``E * sum_e f_e P_e`` with ``f_e`` the share of the T * K selections that chose expert e
+    (detached) and ``P_e`` the mean router probability of e; 1 at perfect balance, 0 when
+    T = 0.  It is not scaled: ``aux_loss_coef`` is only stored, for the caller's
+    ``loss + layer.aux_loss_coef * layer.aux_loss``."""
 
     def __init__(self, group, d_model: int, d_ff: int, num_experts: int, top_k: int, capacity: int,
-                 renormalize: bool = True, dtype=torch.bfloat16):
+                 renormalize: bool = True, dtype=torch.bfloat16, expert_capacity=None, gate: str = "torch",
+                 aux_loss_coef: float = 0.0):
         super().__init__()
         dev = _dev(group)
         if num_experts < 1 or num_experts % dev.size:
@@ -137,19 +162,50 @@ class RoutedMoE(torch.nn.Module):
             raise ValueError("RoutedMoE: top_k must be in [1, min(8, num_experts)]")
         if capacity < 1:
             raise ValueError("RoutedMoE: capacity must be at least one row")
+        if gate not in ("torch", "fused"):
+            raise ValueError(f"RoutedMoE: gate must be 'torch' or 'fused', got {gate!r}")
+        if expert_capacity is not None:
+            expert_capacity = int(expert_capacity)
+            if expert_capacity < 1:
+                raise ValueError("RoutedMoE: expert_capacity must be at least 1")
+            if capacity < (num_experts // dev.size) * expert_capacity:
+                raise ValueError(f"RoutedMoE: capacity ({capacity}) must be at least (num_experts / p) * "
+                                 f"expert_capacity = {(num_experts // dev.size) * expert_capacity}")
         self.group, self.num_experts, self.top_k, self.capacity = dev, num_experts, top_k, int(capacity)
         self.renormalize = renormalize
+        self.expert_capacity, self.gate, self.aux_loss_coef = expert_capacity, gate, float(aux_loss_coef)
+        self.aux_loss = None
         self.router = torch.nn.Parameter(torch.randn(num_experts, d_model, device=dev.device, dtype=torch.float32)
                                          / math.sqrt(d_model))
         self.experts = GroupedExpertsMLP(num_experts // dev.size, d_model, d_ff, device=dev.device, dtype=dtype)
         self.last_handle = None
 
+    @staticmethod
+    def capacity_for(tokens_all_ranks: int, top_k: int, num_experts: int, factor: float = 1.0) -> int:
+        """The per-expert capacity ``ceil(factor * tokens_all_ranks * top_k / num_experts)``:
+        ``factor`` times an expert's rows under perfectly balanced routing."""
+        return int(math.ceil(factor * tokens_all_ranks * top_k / num_experts))
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        probs = torch.softmax(x.float() @ self.router.t(), dim=-1)
-        w, idx = probs.topk(self.top_k, dim=-1)
-        if self.renormalize:
-            w = w / w.sum(dim=-1, keepdim=True)
-        recv_x, h = moe_dispatch(self.group, x, idx, self.num_experts, self.capacity)
+        T = x.shape[0]
+        logits = x.float() @ self.router.t()
+        if self.gate == "fused":
+            w, idx, prob_sum, expert_tokens = ops.moe_gate(logits, self.top_k, self.renormalize)
+        else:
+            probs = torch.softmax(logits, dim=-1)
+            w, idx = probs.topk(self.top_k, dim=-1)
+            if self.renormalize:
+                w = w / w.sum(dim=-1, keepdim=True)
+            prob_sum = probs.sum(dim=0)
+            expert_tokens = torch.zeros(self.num_experts, dtype=torch.int64, device=x.device)
+            expert_tokens.scatter_add_(0, idx.reshape(-1), torch.ones_like(idx.reshape(-1)))
+        if T:
+            f = expert_tokens.detach().to(torch.float32) / float(T * self.top_k)
+            self.aux_loss = self.num_experts * (f * (prob_sum / float(T))).sum()
+        else:
+            self.aux_loss = prob_sum.sum() * 0.0
+        recv_x, h = moe_dispatch(self.group, x, idx, self.num_experts, self.capacity,
+                                 expert_capacity=self.expert_capacity)
         self.last_handle = h
         y = self.experts(recv_x, h.expert_counts)
         return moe_combine(self.group, y, h, w)
