@@ -17,6 +17,9 @@
 // (row & 7) so a 16-lane ds_read_b128 group touches 8 different slots.
 // Workgroup ids are remapped so that consecutive N-tiles of one M-row of
 // tiles land on the same XCD (shared A panel in that XCD's L2).
+// The tile's main loops and value-described epilogues are in gemm_tile128.hpp,
+// shared with the grouped expert kernels (grouped_gemm.hip); the kernels here
+// are workgroup-to-tile mapping + split-K range + loop + epilogue choice.
 #include <pybind11/pybind11.h>
 
 #include <algorithm>
@@ -25,6 +28,7 @@
 
 #include "common.hpp"
 #include "gemm_common.hpp"
+#include "gemm_tile128.hpp"
 #include "ops.hpp"
 
 namespace ccmpi {
@@ -33,7 +37,6 @@ namespace dev {
 namespace {
 using namespace gemm;
 
-constexpr int BM = 128, BN = 128, BK = 64, NT = 256;
 bool g_use_glds = std::getenv("CCMPI_GEMM_NO_GLDS") == nullptr;  // A/B switch (benchmarks)
 bool g_direct_epi = std::getenv("CCMPI_GEMM_STAGED_EPI") == nullptr;  // LDS-free epilogue (A/B switch)
 // (round 1 also carried a BK = 32, a multi-stage (3-5 x 16 KiB) and a persistent
@@ -41,7 +44,6 @@ bool g_direct_epi = std::getenv("CCMPI_GEMM_STAGED_EPI") == nullptr;  // LDS-fre
 // (profiles/r1_qkv_reassoc/qkv_shapes2.txt, profiles/r1_gemm_fastepi) and were removed)
 // kernel choice for gemm_nt: 0 auto, 1 = 128x128 only, 2 = 256x256 / 3 = 256x128 / 4 = 256x192 whenever legal
 int g_kernel = std::getenv("CCMPI_GEMM_KERNEL") ? std::atoi(std::getenv("CCMPI_GEMM_KERNEL")) : 0;
-constexpr int kRowBytes = BK * 2;  // 128 B per LDS row
 
 // Shared epilogue of the 128x128 kernels: lane holds D[4*(lane>>4) + r][lane & 15]
 // of each 16x16 tile.  Stage the (alpha, bias, act)-applied fp32 tile through
@@ -63,54 +65,9 @@ __device__ __forceinline__ void store_tile(const GemmArgs& g, floatx4 (&acc)[4][
   store_rows<BM, BN, NT>(g, tile, TS, bm, bn, t);
 }
 
-// Branch-free staged epilogue of the weight-gradient GEMM (fp32 C, alpha only):
-// ATOMIC = split-K partial sums as lane-consecutive fp32 atomics, otherwise
-// plain (or accumulating) 16-B row stores.
-template <bool ATOMIC, bool ACCUM>
-__device__ __forceinline__ void store_tile_f32(const GemmArgs& g, floatx4 (&acc)[4][4], unsigned char* smem, int bm,
-                                              int bn, int wm, int wn, int t, int lane) {
-  float* tile = reinterpret_cast<float*>(smem);
-  constexpr int TS = BN + 4;
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        tile[(wm + i * 16 + (lane >> 4) * 4 + r) * TS + wn + j * 16 + (lane & 15)] = g.alpha * acc[i][j][r];
-  __syncthreads();
-  if constexpr (ATOMIC) {
-    for (int idx = t; idx < BM * BN; idx += NT) {
-      const int rl = idx / BN, cl = idx % BN;
-      const int row = bm + rl, col = bn + cl;
-      if (row < g.M && col < g.N) atomicAdd(reinterpret_cast<float*>(g.C) + (size_t)row * g.ldc + col, tile[rl * TS + cl]);
-    }
-  } else {
-    for (int idx = t; idx < BM * (BN / 4); idx += NT) {
-      const int rl = idx / (BN / 4), cl = (idx % (BN / 4)) * 4;
-      const int row = bm + rl, col = bn + cl;
-      if (row >= g.M || col >= g.N) continue;
-      float4* C = reinterpret_cast<float4*>(reinterpret_cast<float*>(g.C) + (size_t)row * g.ldc + col);
-      float4 v = make_float4(tile[rl * TS + cl], tile[rl * TS + cl + 1], tile[rl * TS + cl + 2], tile[rl * TS + cl + 3]);
-      if constexpr (ACCUM) {
-        const float4 o = *C;
-        v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w;
-      }
-      *C = v;
-    }
-  }
-}
-
-// Direct (LDS-free) epilogue for kernels that swap the MFMA operands and stage
-// B rows in the "pair" permutation: LDS row 32p + 16h + q of the B tile holds
-// output column 32p + 8*(q >> 2) + 4h + (q & 3).  The accumulator of tile
-// (i, j = 2p + h) then holds C[row0 + 16i + (lane & 15)][col0 + 32p + 8*(lane >> 4) + 4h + r],
-// i.e. 8 consecutive columns of one row per lane and pair: one 16-B vector store
-// (bf16) or two (fp32).  Split-K partials go out as fp32 atomics.
-__device__ __forceinline__ int pair_perm(int r) {
-  return (r & ~31) | (((r & 15) >> 2) << 3) | (((r >> 4) & 1) << 2) | (r & 3);
-}
-
+// Generic direct (LDS-free) epilogue for the loops that swap the MFMA operands and
+// stage B rows in the pair permutation (gemm_tile128.hpp: 8 consecutive columns of
+// one row per lane and pair).  Split-K partials go out as fp32 atomics.
 __device__ __forceinline__ void store_direct(const GemmArgs& g, const floatx4 (&acc)[4][4], int row0, int col0, int split,
                                              int lane) {
   const int c = lane & 15, gq = lane >> 4;
@@ -173,223 +130,59 @@ __device__ __forceinline__ void store_direct(const GemmArgs& g, const floatx4 (&
   }
 }
 
-// Branch-free specialization of store_direct for the common case (splitk 1, no
-// accumulate, no activation, 16-B aligned C, N % 8 == 0): output type and bias
-// kind are compile-time, so the epilogue is straight-line code (the generic one
-// unrolls every runtime combination into ~12k instructions).
-template <bool OUT_BF16, int BIAS>
-__device__ __forceinline__ void store_direct_fast(const GemmArgs& g, const floatx4 (&acc)[4][4], int row0, int col0,
-                                                  int lane) {
-  const int c = lane & 15, gq = lane >> 4;
-#pragma unroll
-  for (int p = 0; p < 2; ++p) {
-    const int col = col0 + 32 * p + 8 * gq;
-    float bias[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      if constexpr (BIAS == 1) bias[e] = col < g.N ? reinterpret_cast<const float*>(g.bias)[col + e] : 0.f;
-      else if constexpr (BIAS == 2) bias[e] = col < g.N ? bf2f(reinterpret_cast<const uint16_t*>(g.bias)[col + e]) : 0.f;
-      else bias[e] = 0.f;
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int row = row0 + 16 * i + c;
-      float v[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) v[e] = g.alpha * acc[i][2 * p + (e >> 2)][e & 3] + bias[e];
-      if (row < g.M && col < g.N) {
-        if constexpr (OUT_BF16) {
-          uint32_t w[4];
-#pragma unroll
-          for (int q = 0; q < 4; ++q) w[q] = pk_bf16(v[2 * q], v[2 * q + 1]);
-          *reinterpret_cast<uint4*>(reinterpret_cast<uint16_t*>(g.C) + (size_t)row * g.ldc + col) =
-              uint4{w[0], w[1], w[2], w[3]};
-        } else {
-          float4* C = reinterpret_cast<float4*>(reinterpret_cast<float*>(g.C) + (size_t)row * g.ldc + col);
-          C[0] = make_float4(v[0], v[1], v[2], v[3]);
-          C[1] = make_float4(v[4], v[5], v[6], v[7]);
-        }
-      }
-    }
-  }
+// K tiles [kt0, kt0 + nk) of nk_all that split `split` of a split-K launch walks
+__device__ __forceinline__ void split_tiles(int nk_all, int splitk, int split, int& kt0, int& nk) {
+  const int per = (nk_all + splitk - 1) / splitk;
+  kt0 = split * per;
+  nk = max(0, min(nk_all, kt0 + per) - kt0);
 }
 
+// Register-staged 128x128 kernel (nt_loop_regs), for any K % 8 == 0; LDS-staged epilogue.
 __global__ void __launch_bounds__(NT) k_gemm_nt(GemmArgs g) {
-  __shared__ __attribute__((aligned(16))) unsigned char smem[(2 * (BM + BN) * kRowBytes > BM * (BN + 4) * 4) ? 2 * (BM + BN) * kRowBytes : BM * (BN + 4) * 4];
+  __shared__ __attribute__((aligned(16))) unsigned char smem[kNtLoopBytes > kEpiBytes ? kNtLoopBytes : kEpiBytes];
   const int tiles_n = (g.N + BN - 1) / BN, tiles_m = (g.M + BM - 1) / BM;
-  const int nwg = tiles_n * tiles_m * g.splitk;
   // bijective XCD-aware remap: blocks b, b+8, b+16, ... (same XCD) get consecutive ids;
   // the K slices of one tile are adjacent ids, so they share an XCD (and its L2)
-  int wg = blockIdx.x;
-  {
-    const int q = nwg / 8, r = nwg % 8, x = wg % 8;
-    wg = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + wg / 8;
-  }
+  int wg = xcd_remap(blockIdx.x, tiles_n * tiles_m * g.splitk);
   const int split = wg % g.splitk;
   wg /= g.splitk;
   const int bm = (wg / tiles_n) * BM, bn = (wg % tiles_n) * BN;
   const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
   const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
 
-  auto As = [&](int buf) { return smem + buf * ((BM + BN) * kRowBytes); };
-  auto Bs = [&](int buf) { return smem + buf * ((BM + BN) * kRowBytes) + BM * kRowBytes; };
-
   floatx4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = floatx4{0.f, 0.f, 0.f, 0.f};
-
-  uint4 ra[4], rb[4];
-  const int srow = t >> 3, schunk = t & 7;
-  auto gload = [&](int k0) {
-    const int gk = k0 + schunk * 8;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int r = srow + 32 * i;
-      const int gm = bm + r, gn = bn + r;
-      ra[i] = (gm < g.M && gk < g.K) ? *reinterpret_cast<const uint4*>(g.A + (size_t)gm * g.lda + gk) : uint4{0, 0, 0, 0};
-      rb[i] = (gn < g.N && gk < g.K) ? *reinterpret_cast<const uint4*>(g.B + (size_t)gn * g.ldb + gk) : uint4{0, 0, 0, 0};
-    }
-  };
-  auto swrite = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int r = srow + 32 * i;
-      const int off = r * kRowBytes + ((schunk ^ (r & 7)) << 4);
-      *reinterpret_cast<uint4*>(As(buf) + off) = ra[i];
-      *reinterpret_cast<uint4*>(Bs(buf) + off) = rb[i];
-    }
-  };
-
-  const int nk_all = (g.K + BK - 1) / BK;
-  const int per = (nk_all + g.splitk - 1) / g.splitk;
-  const int kt0 = split * per;
-  const int nk = max(0, min(nk_all, kt0 + per) - kt0);
-  if (nk > 0) {
-    gload(kt0 * BK);
-    swrite(0);
-  }
-  __syncthreads();
-  for (int kt = 0; kt < nk; ++kt) {
-    const int cur = kt & 1;
-    if (kt + 1 < nk) gload((kt0 + kt + 1) * BK);
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      bf16x8 af[4], bf[4];
-      const int chunk = ks * 4 + (lane >> 4);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int ra_ = wm + i * 16 + (lane & 15);
-        af[i] = *reinterpret_cast<const bf16x8*>(As(cur) + ra_ * kRowBytes + ((chunk ^ (ra_ & 7)) << 4));
-        const int rb_ = wn + i * 16 + (lane & 15);
-        bf[i] = *reinterpret_cast<const bf16x8*>(Bs(cur) + rb_ * kRowBytes + ((chunk ^ (rb_ & 7)) << 4));
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bf[j], acc[i][j], 0, 0, 0);
-    }
-    if (kt + 1 < nk) swrite(cur ^ 1);
-    __syncthreads();
-  }
+  int kt0, nk;
+  split_tiles((g.K + BK - 1) / BK, g.splitk, split, kt0, nk);
+  nt_loop_regs<false>(NtSrc{g.A, g.B, g.lda, g.ldb, bm, g.M, bn, g.N, g.K, kt0, nk}, smem, acc, wave, t);
 
   __syncthreads();
   store_tile(g, acc, smem, bm, bn, wm, wn, split, t, lane);
 }
 
-// Same tile / wave layout as k_gemm_nt, staged by LDS-DMA (global_load_lds,
-// 16 B per lane, 1 KiB per wave instruction) instead of registers: the next
-// K-tile streams straight into the other LDS buffer while this one feeds the
-// MFMAs, and the staging costs no VGPRs and no ds_write issue slots.  The LDS
-// image is lane-linear (8 rows of 128 B per instruction), so the (row & 7)
-// chunk swizzle the fragment reads expect is applied to the per-lane SOURCE
-// address (the same involution on both sides).  Rows past M / N re-read the
-// last valid row (their outputs are discarded); used only when K % 64 == 0.
+// Same tile / wave layout as k_gemm_nt, staged by LDS-DMA (nt_loop_glds); used only
+// when K % 64 == 0.
 __constant__ int g_pp_exp_dev = 0;
 
 // DIRECT: swapped MFMA operands + pair-permuted B staging + LDS-free epilogue
 // (store_direct); otherwise the LDS-staged row epilogue (store_tile).
 template <bool DIRECT, int FAST = 0>  // FAST = 1 + out_bf16 + 2 * bias_kind (store_direct_fast), 0 = generic
 __global__ void __launch_bounds__(NT) k_gemm_nt_glds(GemmArgs g) {
-  constexpr int kLoop = 2 * (BM + BN) * kRowBytes, kEpi = DIRECT ? 0 : BM * (BN + 4) * 4;
-  __shared__ __attribute__((aligned(16))) unsigned char smem[kLoop > kEpi ? kLoop : kEpi];
+  constexpr int kEpi = DIRECT ? 0 : kEpiBytes;
+  __shared__ __attribute__((aligned(16))) unsigned char smem[kNtLoopBytes > kEpi ? kNtLoopBytes : kEpi];
   const int tiles_n = (g.N + BN - 1) / BN, tiles_m = (g.M + BM - 1) / BM;
-  const int nwg = tiles_n * tiles_m * g.splitk;
-  int wg = blockIdx.x;
-  {
-    const int q = nwg / 8, r = nwg % 8, x = wg % 8;
-    wg = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + wg / 8;
-  }
+  int wg = xcd_remap(blockIdx.x, tiles_n * tiles_m * g.splitk);
   const int split = wg % g.splitk;
   wg /= g.splitk;
   const int bm = (wg / tiles_n) * BM, bn = (wg % tiles_n) * BN;
   const int t = threadIdx.x, lane = t & 63;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
-  auto As = [&](int buf) { return smem + buf * ((BM + BN) * kRowBytes); };
-  auto Bs = [&](int buf) { return smem + buf * ((BM + BN) * kRowBytes) + BM * kRowBytes; };
 
   floatx4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = floatx4{0.f, 0.f, 0.f, 0.f};
+  int kt0, nk;
+  split_tiles(g.K / BK, g.splitk, split, kt0, nk);
+  nt_loop_glds<DIRECT>(NtSrc{g.A, g.B, g.lda, g.ldb, bm, g.M, bn, g.N, g.K, kt0, nk}, smem, acc, wave, lane);
 
-  // per-lane source row / swizzled chunk for the 4 instructions of this wave
-  const int lrow = lane >> 3, pchunk = lane & 7;
-  auto issue = [&](int k0, int buf) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int q = wave * 4 + i;                 // 1 KiB LDS chunk = rows q*8 .. q*8+7
-      const int r = q * 8 + lrow;
-      const int c = pchunk ^ (r & 7);             // logical k-chunk this lane must fetch
-      const int ga = min(bm + r, g.M - 1), gb = min(bn + (DIRECT ? pair_perm(r) : r), g.N - 1);
-      __builtin_amdgcn_global_load_lds((const void*)(g.A + (size_t)ga * g.lda + k0 + c * 8),
-                                       (__attribute__((address_space(3))) void*)(As(buf) + q * 1024), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds((const void*)(g.B + (size_t)gb * g.ldb + k0 + c * 8),
-                                       (__attribute__((address_space(3))) void*)(Bs(buf) + q * 1024), 16, 0, 0);
-    }
-  };
-  const int nk_all = g.K / BK;
-  const int per = (nk_all + g.splitk - 1) / g.splitk;
-  const int kt0 = split * per;
-  const int nk = max(0, min(nk_all, kt0 + per) - kt0);
-  if (nk > 0) issue(kt0 * BK, 0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  for (int kt = 0; kt < nk; ++kt) {
-    const int cur = kt & 1;
-    // all fragment reads of this K-tile BEFORE the next tile's DMA is issued:
-    // the compiler cannot prove the DMA target disjoint from the reads and
-    // would otherwise wait for the DMA before the remaining ds_reads
-    bf16x8 af[2][4], bf[2][4];
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const int chunk = ks * 4 + (lane >> 4);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int ra_ = wm + i * 16 + (lane & 15);
-        af[ks][i] = *reinterpret_cast<const bf16x8*>(As(cur) + ra_ * kRowBytes + ((chunk ^ (ra_ & 7)) << 4));
-        const int rb_ = wn + i * 16 + (lane & 15);
-        bf[ks][i] = *reinterpret_cast<const bf16x8*>(Bs(cur) + rb_ * kRowBytes + ((chunk ^ (rb_ & 7)) << 4));
-      }
-    }
-    if (kt + 1 < nk) issue((kt0 + kt + 1) * BK, cur ^ 1);
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          if constexpr (DIRECT) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[ks][j], af[ks][i], acc[i][j], 0, 0, 0);
-          else acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[ks][i], bf[ks][j], acc[i][j], 0, 0, 0);
-        }
-    __builtin_amdgcn_s_setprio(0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-  }
   if (g_pp_exp_dev & 8) {  // ablation (benchmarks only): no epilogue, accumulators kept live
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -399,32 +192,20 @@ __global__ void __launch_bounds__(NT) k_gemm_nt_glds(GemmArgs g) {
   }
   constexpr bool kFastBf16 = ((FAST - 1) & 1) != 0;
   constexpr int kFastBias = (FAST - 1) / 2;
-  if constexpr (DIRECT && FAST > 0) store_direct_fast<kFastBf16, kFastBias>(g, acc, bm + wm, bn + wn, lane);
+  if constexpr (DIRECT && FAST > 0)
+    store_direct_fast<kFastBf16>(TileDst{g.C, g.ldc, g.M, g.N, g.alpha, g.bias, kFastBias}, acc, bm + wm, bn + wn, lane);
   else if constexpr (DIRECT) store_direct(g, acc, bm + wm, bn + wn, split, lane);
   else store_tile(g, acc, smem, bm, bn, wm, wn, split, t, lane);
 }
 
-
-
 // ---------------------------------------------------------------------------
 // "TN" GEMM for weight gradients: C[N1,N2] (+)= alpha * sum_m A[m,n1] * B[m,n2]
 // with A [M][N1] and B [M][N2] row-major (n contiguous), i.e. dW = dY^T X
-// without materialising any transpose.  Tiles of 64 m-rows x 128 columns are
-// staged as-is into LDS; MFMA operands (8 consecutive m for one column per
-// lane) come out of gfx950's transposing LDS read ds_read_b64_tr_b16, two
-// reads per operand per 32-deep k-step.  LDS rows are 256 B + 32 B pad (row r
-// starts 8 banks after row r-1) and the two 128-B halves of rows with bit 3
-// set are swapped, so every tr read (a 32-lane half spans rows r..r+3 and
-// r+8..r+11) is bank-conflict free.  K (= batch*seq) is long and M, N small:
-// the split-K grid fills the chip and partial tiles meet through fp32
+// without materialising any transpose (gemm_tile128.hpp: tn_stage, tn_compute --
+// operands through the transposing LDS read).  K (= batch*seq) is long and M, N
+// small: the split-K grid fills the chip and partial tiles meet through fp32
 // atomic adds.
 // ---------------------------------------------------------------------------
-typedef short v4s __attribute__((ext_vector_type(4)));
-constexpr int kTnRow = 288;             // bytes per LDS row (256 data + 32 pad)
-constexpr int kTnTile = BK * kTnRow;    // one operand tile
-
-__device__ __forceinline__ int tn_off(int row, int byte) { return row * kTnRow + (byte ^ (((row >> 3) & 1) << 7)); }
-
 // FAST: 0 generic store_tile, 1 split-K atomics, 2 plain stores, 3 accumulating stores,
 // 4 split-K partial into a workspace slice (fp32 C, 16-B aligned, N2 % 4 == 0).
 // split_major = 1: logical id = split * tiles + tile, so after the XCD remap one XCD
@@ -437,17 +218,15 @@ __device__ __forceinline__ int tn_off(int row, int byte) { return row * kTnRow +
 // the sets are indexed statically): 5-8 % faster on the dQKV^T Xp and 4096^2 shapes.  PF = 4
 // (one wave per SIMD) measured no faster on the narrow shape and 20 % slower on the wide ones
 // (profiles/r5_train_kernels/gemm_tn_pf4.jsonl), so only 1 and 2 are built.
+// The loads and the schedule are the kernel's own (the grouped weight gradient runs the same
+// schedule as tn_loop_pf2): through the shared loop the compiler formed this kernel's load
+// addresses differently and it measured slower (profiles/gemm_tile128/README.md).
 template <int FAST, int PF = 1>
 __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(PF >= 4 ? 1 : 2))) k_gemm_tn(GemmArgs g, int split_major) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[4 * kTnTile];
   // here: g.M = N1 (rows of C), g.N = N2 (cols of C), g.K = M (reduction)
   const int tiles_n = (g.N + BN - 1) / BN, tiles_m = (g.M + BM - 1) / BM;
-  const int nwg = tiles_n * tiles_m * g.splitk;
-  int wg = blockIdx.x;
-  {
-    const int q = nwg / 8, r = nwg % 8, x = wg % 8;
-    wg = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + wg / 8;
-  }
+  int wg = xcd_remap(blockIdx.x, tiles_n * tiles_m * g.splitk);
   int split;
   if (split_major) {
     split = wg / (tiles_n * tiles_m);
@@ -459,21 +238,14 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(PF >= 4
   const int bm = (wg / tiles_n) * BM, bn = (wg % tiles_n) * BN;
   const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
   const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
-  auto As = [&](int buf) { return smem + buf * (2 * kTnTile); };
-  auto Bs = [&](int buf) { return smem + buf * (2 * kTnTile) + kTnTile; };
 
   floatx4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = floatx4{0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
 
   uint4 ra[PF][4], rb[PF][4];
   const int schunk = t & 15, srow = t >> 4;  // 16 chunks of 16 B per 128-column row
-  const int nk_all = (g.K + BK - 1) / BK;
-  const int per = (nk_all + g.splitk - 1) / g.splitk;
-  const int kt0 = split * per;
-  const int nk = max(0, min(nk_all, kt0 + per) - kt0);
+  int kt0, nk;
+  split_tiles((g.K + BK - 1) / BK, g.splitk, split, kt0, nk);
   // PF = 2 loads through buffer resources over this split's rows: rows past K read as 0
   // with no branch, so the loads carry no exec-mask control flow and the compiler can
   // wait for the older register set alone (with the guarded pointer loads below it
@@ -502,47 +274,8 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(PF >= 4
       }
     }
   };
-  auto swrite = [&](int buf, int s) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int r = srow + 16 * i;
-      *reinterpret_cast<uint4*>(As(buf) + tn_off(r, schunk * 16)) = ra[s][i];
-      *reinterpret_cast<uint4*>(Bs(buf) + tn_off(r, schunk * 16)) = rb[s][i];
-    }
-  };
-  const int grp = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
-  // fragment read addresses: tn_off(ks * 32 + grp * 8 + q + 4 h, (w + 16 i + 4 p) * 2) is a
-  // per-lane base plus the constant ks * 32 * kTnRow + h * 4 * kTnRow + 32 i: the half-swap
-  // XOR only flips the 128-B bit that w * 2 (w in {0, 64}) owns (row bit 3 = grp & 1; q + 4h
-  // < 8 never carries into it), so every read is base + an immediate offset
-  const int lrow = (grp * 8 + q) * kTnRow, xsw = (grp & 1) << 7;
-  const int la = lrow + ((wm * 2) ^ xsw) + 8 * p, lb = lrow + ((wn * 2) ^ xsw) + 8 * p;
-  auto compute = [&](int cur) {
-    const unsigned char* abase = As(cur) + la;
-    const unsigned char* bbase = Bs(cur) + lb;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      bf16x8 af[4], bf[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        v4s a0, a1, b0, b1;
-        const int o = ks * 32 * kTnRow + 32 * i;
-        a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s*)(abase + o));
-        a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s*)(abase + o + 4 * kTnRow));
-        b0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s*)(bbase + o));
-        b1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s*)(bbase + o + 4 * kTnRow));
-        typedef short v8s __attribute__((ext_vector_type(8)));
-        v8s av = __builtin_shufflevector(a0, a1, 0, 1, 2, 3, 4, 5, 6, 7);
-        v8s bv = __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7);
-        af[i] = __builtin_bit_cast(bf16x8, av);
-        bf[i] = __builtin_bit_cast(bf16x8, bv);
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bf[j], acc[i][j], 0, 0, 0);
-    }
-  };
+  auto swrite = [&](int buf, int s) { tn_stage(smem, buf, ra[s], rb[s], t); };
+  auto compute = [&](int cur) { tn_compute(smem, cur, acc, t); };
   if constexpr (PF == 1) {
     if (nk > 0) {
       gload(0, kt0 * BK);
@@ -578,14 +311,13 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(PF >= 4
     }
   }
   __syncthreads();
-  if constexpr (FAST == 1) store_tile_f32<true, false>(g, acc, smem, bm, bn, wm, wn, t, lane);
+  const TileDst d{g.C, g.ldc, g.M, g.N, g.alpha, nullptr, 0};
+  if constexpr (FAST == 1) store_tile_f32<true, false>(d, acc, smem, bm, bn, t);
   else if constexpr (FAST == 4) {  // split-K partial -> workspace slice [split][N1][N2] (plain stores)
-    GemmArgs w = g;
-    w.C = reinterpret_cast<float*>(g.C) + (size_t)split * g.M * g.N;
-    w.ldc = g.N;
-    store_tile_f32<false, false>(w, acc, smem, bm, bn, wm, wn, t, lane);
-  } else if constexpr (FAST == 2) store_tile_f32<false, false>(g, acc, smem, bm, bn, wm, wn, t, lane);
-  else if constexpr (FAST == 3) store_tile_f32<false, true>(g, acc, smem, bm, bn, wm, wn, t, lane);
+    const TileDst w{reinterpret_cast<float*>(g.C) + (size_t)split * g.M * g.N, g.N, g.M, g.N, g.alpha, nullptr, 0};
+    store_tile_f32<false, false>(w, acc, smem, bm, bn, t);
+  } else if constexpr (FAST == 2) store_tile_f32<false, false>(d, acc, smem, bm, bn, t);
+  else if constexpr (FAST == 3) store_tile_f32<false, true>(d, acc, smem, bm, bn, t);
   else store_tile(g, acc, smem, bm, bn, wm, wn, split, t, lane);
 }
 
@@ -1129,6 +861,18 @@ int g_tn_split_major = std::getenv("CCMPI_TN_ORDER") ? std::atoi(std::getenv("CC
 // K tiles in flight in the 128x128 TN kernel: 0 = auto (two when a split walks >= 4 tiles), 1, 2
 int g_tn_pf = std::getenv("CCMPI_TN_PF") ? std::atoi(std::getenv("CCMPI_TN_PF")) : 0;
 
+// k_gemm_tn<fast, PF> for the epilogue id `fast` chosen by gemm_tn
+template <int PF>
+void launch_gemm_tn(int fast, int nwg, hipStream_t st, const GemmArgs& g) {
+  switch (fast) {
+    case 4: hipLaunchKernelGGL((k_gemm_tn<4, PF>), dim3(nwg), dim3(NT), 0, st, g, g_tn_split_major); break;
+    case 1: hipLaunchKernelGGL((k_gemm_tn<1, PF>), dim3(nwg), dim3(NT), 0, st, g, g_tn_split_major); break;
+    case 2: hipLaunchKernelGGL((k_gemm_tn<2, PF>), dim3(nwg), dim3(NT), 0, st, g, g_tn_split_major); break;
+    case 3: hipLaunchKernelGGL((k_gemm_tn<3, PF>), dim3(nwg), dim3(NT), 0, st, g, g_tn_split_major); break;
+    default: hipLaunchKernelGGL((k_gemm_tn<0, PF>), dim3(nwg), dim3(NT), 0, st, g, g_tn_split_major); break;
+  }
+}
+
 // C[N1,N2] (+)= alpha * A[M,N1]^T . B[M,N2]; fp32 output.
 void gemm_tn(uint64_t A, uint64_t B, uint64_t C, int M, int N1, int N2, int lda, int ldb, int ldc, float alpha,
              bool accumulate, int splitk, uint64_t stream, uint64_t workspace, int variant, uint64_t C2, int ldc2,
@@ -1143,24 +887,25 @@ void gemm_tn(uint64_t A, uint64_t B, uint64_t C, int M, int N1, int N2, int lda,
   if (N1 % 8 || N2 % 8 || lda % 8 || ldb % 8 || (A % 16) || (B % 16))
     throw std::invalid_argument("ccmpi gemm_tn: N1, N2, lda, ldb must be multiples of 8 and A/B 16-B aligned");
   if (splitk < 1) splitk = 1;
+  auto st = reinterpret_cast<hipStream_t>(stream);
+  auto reduce_splits = [&] {  // C (+)= the sum of the workspace's splitk slices (columns >= csplit to C2)
+    const size_t work = (size_t)N1 * (N2 / 4);
+    const int grid = (int)std::min<size_t>((work + 255) / 256, 4096);
+    hipLaunchKernelGGL(k_splitk_reduce, dim3(grid), dim3(256), 0, st, reinterpret_cast<const float*>(workspace), splitk,
+                       reinterpret_cast<float*>(C), ldc, N1, N2, accumulate ? 1 : 0,
+                       reinterpret_cast<float*>(C2), ldc2, csplit);
+    CCMPI_HIP_CHECK(hipGetLastError());
+  };
   // variant 1: 256x256 8-wave ping-pong TN kernel (gemm256.hip); partials of every
   // split go to workspace slices, then k_splitk_reduce
   if (variant == 1 && M % 128 == 0 && N1 >= 256 && N2 >= 256 && (C % 16) == 0 && ldc % 4 == 0 &&
       (splitk == 1 || (workspace != 0 && (workspace % 16) == 0))) {
-    auto st = reinterpret_cast<hipStream_t>(stream);
     GemmArgs g{reinterpret_cast<const uint16_t*>(A), reinterpret_cast<const uint16_t*>(B),
                reinterpret_cast<void*>(splitk > 1 ? workspace : C), nullptr, N1, N2, M, lda, ldb,
                splitk > 1 ? N2 : ldc, alpha, (splitk == 1 && accumulate) ? 1 : 0, 0, 0, 0, splitk};
     launch_gemm_tn_256(g, st);
     CCMPI_HIP_CHECK(hipGetLastError());
-    if (splitk > 1) {
-      const size_t work = (size_t)N1 * (N2 / 4);
-      const int grid = (int)std::min<size_t>((work + 255) / 256, 4096);
-      hipLaunchKernelGGL(k_splitk_reduce, dim3(grid), dim3(256), 0, st, reinterpret_cast<const float*>(workspace), splitk,
-                         reinterpret_cast<float*>(C), ldc, N1, N2, accumulate ? 1 : 0,
-                         reinterpret_cast<float*>(C2), ldc2, csplit);
-      CCMPI_HIP_CHECK(hipGetLastError());
-    }
+    if (splitk > 1) reduce_splits();
     return;
   }
   // split-K partials: a workspace of splitk fp32 slices summed by k_splitk_reduce
@@ -1176,48 +921,15 @@ void gemm_tn(uint64_t A, uint64_t B, uint64_t C, int M, int N1, int N2, int lda,
   const int nwg = ((N1 + BM - 1) / BM) * ((N2 + BN - 1) / BN) * splitk;
   const bool aligned = (C % 16) == 0 && ldc % 4 == 0 && N2 % 4 == 0;
   const int fast = use_ws ? 4 : !aligned ? 0 : splitk > 1 ? 1 : accumulate ? 3 : 2;
-  auto st = reinterpret_cast<hipStream_t>(stream);
   // two K tiles in flight when each workgroup walks several of them (g_tn_pf: A/B knob)
   const int nk_split = ((M + BK - 1) / BK + splitk - 1) / splitk;
   // (PF = 2 addresses a split's rows with 32-bit buffer offsets)
   const bool fits = (size_t)nk_split * BK * std::max(lda, ldb) * 2 < (1ull << 31);
   const bool pf2 = fits && (g_tn_pf == 2 || (g_tn_pf == 0 && nk_split >= 4));
-  if (pf2) {
-    switch (fast) {
-      case 4: hipLaunchKernelGGL((k_gemm_tn<4, 2>), dim3(nwg), dim3(NT), 0, st, g, g_tn_split_major); break;
-      case 1: hipLaunchKernelGGL((k_gemm_tn<1, 2>), dim3(nwg), dim3(NT), 0, st, g, g_tn_split_major); break;
-      case 2: hipLaunchKernelGGL((k_gemm_tn<2, 2>), dim3(nwg), dim3(NT), 0, st, g, g_tn_split_major); break;
-      case 3: hipLaunchKernelGGL((k_gemm_tn<3, 2>), dim3(nwg), dim3(NT), 0, st, g, g_tn_split_major); break;
-      default: hipLaunchKernelGGL((k_gemm_tn<0, 2>), dim3(nwg), dim3(NT), 0, st, g, g_tn_split_major); break;
-    }
-    CCMPI_HIP_CHECK(hipGetLastError());
-    if (fast == 4) {
-      const size_t work = (size_t)N1 * (N2 / 4);
-      const int grid = (int)std::min<size_t>((work + 255) / 256, 4096);
-      hipLaunchKernelGGL(k_splitk_reduce, dim3(grid), dim3(256), 0, st, reinterpret_cast<const float*>(workspace), splitk,
-                         reinterpret_cast<float*>(C), ldc, N1, N2, accumulate ? 1 : 0,
-                         reinterpret_cast<float*>(C2), ldc2, csplit);
-      CCMPI_HIP_CHECK(hipGetLastError());
-    }
-    return;
-  }
-  switch (fast) {
-    case 4: {
-      hipLaunchKernelGGL(k_gemm_tn<4>, dim3(nwg), dim3(NT), 0, st, g, g_tn_split_major);
-      CCMPI_HIP_CHECK(hipGetLastError());
-      const size_t work = (size_t)N1 * (N2 / 4);
-      const int grid = (int)std::min<size_t>((work + 255) / 256, 4096);
-      hipLaunchKernelGGL(k_splitk_reduce, dim3(grid), dim3(256), 0, st, reinterpret_cast<const float*>(workspace), splitk,
-                         reinterpret_cast<float*>(C), ldc, N1, N2, accumulate ? 1 : 0,
-                         reinterpret_cast<float*>(C2), ldc2, csplit);
-      break;
-    }
-    case 1: hipLaunchKernelGGL(k_gemm_tn<1>, dim3(nwg), dim3(NT), 0, st, g, g_tn_split_major); break;
-    case 2: hipLaunchKernelGGL(k_gemm_tn<2>, dim3(nwg), dim3(NT), 0, st, g, g_tn_split_major); break;
-    case 3: hipLaunchKernelGGL(k_gemm_tn<3>, dim3(nwg), dim3(NT), 0, st, g, g_tn_split_major); break;
-    default: hipLaunchKernelGGL(k_gemm_tn<0>, dim3(nwg), dim3(NT), 0, st, g, g_tn_split_major); break;
-  }
+  if (pf2) launch_gemm_tn<2>(fast, nwg, st, g);
+  else launch_gemm_tn<1>(fast, nwg, st, g);
   CCMPI_HIP_CHECK(hipGetLastError());
+  if (fast == 4) reduce_splits();
 }
 
 void transpose16(uint64_t src, uint64_t dst, int R, int C, int lds, int ldd, uint64_t stream) {

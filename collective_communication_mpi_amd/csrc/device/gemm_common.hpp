@@ -1,5 +1,7 @@
-// Shared pieces of the MFMA GEMM kernels (gemm.hip, gemm256.hip): argument
-// block, epilogue math and the LDS-staged row store.
+// Shared pieces of the MFMA GEMM kernels (gemm.hip, gemm256.hip, gemm_w4.hip,
+// grouped_gemm.hip): argument block, epilogue math, the LDS-staged row store and
+// the XCD remap.  The 128x128 tile itself (main loops, value-described epilogues)
+// that gemm.hip and grouped_gemm.hip share is in gemm_tile128.hpp.
 #pragma once
 #include <cstdint>
 

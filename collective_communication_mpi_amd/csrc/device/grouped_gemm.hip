@@ -20,11 +20,13 @@
 // G * ceil(N / 128) * ceil(K / 128) workgroups; each walks its expert's rows in
 // order (no split-K, no atomics: deterministic, independent of the other experts).
 //
-// The tile code is the 128x128, BK = 64 v_mfma_f32_16x16x32_bf16 tile of gemm.hip:
-// LDS-DMA staging with the swapped-operand direct epilogue when K % 64 == 0, the
-// register-staged loop with a zero-filled K tail otherwise (same LDS image, same
-// epilogue); the weight gradient is k_gemm_tn's two-tiles-in-flight loop over buffer
-// resources that span exactly the expert's rows, so rows past its end load as zero.
+// The tile is the 128x128, BK = 64 v_mfma_f32_16x16x32_bf16 tile of gemm_tile128.hpp,
+// the same code the dense kernels of gemm.hip run: LDS-DMA staging with the
+// swapped-operand direct epilogue when K % 64 == 0, the register-staged loop with a
+// zero-filled K tail otherwise (same LDS image, same epilogue); the weight gradient is
+// the two-tiles-in-flight TN loop over buffer resources that span exactly the expert's
+// rows, so rows past its end load as zero.  The kernels here are what is the experts'
+// own: the counts, the tile search, the grids and the per-expert operand extents.
 #include <pybind11/pybind11.h>
 
 #include <algorithm>
@@ -33,6 +35,7 @@
 
 #include "common.hpp"
 #include "gemm_common.hpp"
+#include "gemm_tile128.hpp"
 #include "ops.hpp"
 
 namespace ccmpi {
@@ -41,8 +44,6 @@ namespace dev {
 namespace {
 using namespace gemm;
 
-constexpr int BM = 128, BN = 128, BK = 64, NT = 256;
-constexpr int kRowBytes = BK * 2;
 constexpr int kMaxGroups = 256;  // = MOE_MAX_EXPERTS (one count per thread of the scan)
 
 struct GroupedArgs {
@@ -91,18 +92,12 @@ __device__ __forceinline__ void expert_rows(const GroupedArgs& a, long long* ws,
   end = (int)(incl < cap ? incl : cap);
 }
 
-// LDS row r of the B tile holds output column pair_perm(r) (gemm.hip: the pair permutation
-// of the direct epilogue)
-__device__ __forceinline__ int pair_perm(int r) {
-  return (r & ~31) | (((r & 15) >> 2) << 3) | (((r >> 4) & 1) << 2) | (r & 3);
-}
-
 // ---------------------------------------------------------------------------
 // forward
 // ---------------------------------------------------------------------------
 template <bool GLDS, bool OUT_BF16>
 __global__ void __launch_bounds__(NT) k_grouped_gemm_nt(GroupedArgs a) {
-  __shared__ __attribute__((aligned(16))) unsigned char smem[2 * (BM + BN) * kRowBytes];
+  __shared__ __attribute__((aligned(16))) unsigned char smem[kNtLoopBytes];
   __shared__ long long ws[4];
   __shared__ int seg[4];  // expert, first row of the tile, end of the expert's rows; row tiles in all
   const int t = threadIdx.x, lane = t & 63;
@@ -135,172 +130,32 @@ __global__ void __launch_bounds__(NT) k_grouped_gemm_nt(GroupedArgs a) {
   const int bm = __builtin_amdgcn_readfirstlane(seg[1]), row_end = __builtin_amdgcn_readfirstlane(seg[2]);
   const uint16_t* Bg = a.B + (size_t)g * a.b_stride;
 
-  const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
-  auto As = [&](int buf) { return smem + buf * ((BM + BN) * kRowBytes); };
-  auto Bs = [&](int buf) { return smem + buf * ((BM + BN) * kRowBytes) + BM * kRowBytes; };
-
+  // Rows past the expert's end / past N are re-read (LDS-DMA) or zero-filled (register
+  // staging, with the K tail) by the shared loops and masked in the store, so nothing
+  // outside the expert's rows is touched.  Both loops stage B pair-permuted and swap the
+  // MFMA operands for the direct epilogue.
   floatx4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = floatx4{0.f, 0.f, 0.f, 0.f};
+  const NtSrc src{a.A, Bg, a.lda, a.ldb, bm, row_end, bn, a.N, a.K, 0, GLDS ? a.K / BK : (a.K + BK - 1) / BK};
+  if constexpr (GLDS) nt_loop_glds<true>(src, smem, acc, wave, lane);
+  else nt_loop_regs<true>(src, smem, acc, wave, t);
 
-  // the MFMAs of one staged K tile; operands swapped (B rows first) for the direct epilogue
-  auto read_frags = [&](int cur, bf16x8 (&af)[2][4], bf16x8 (&bf)[2][4]) {
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const int chunk = ks * 4 + (lane >> 4);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int ra_ = wm + i * 16 + (lane & 15);
-        af[ks][i] = *reinterpret_cast<const bf16x8*>(As(cur) + ra_ * kRowBytes + ((chunk ^ (ra_ & 7)) << 4));
-        const int rb_ = wn + i * 16 + (lane & 15);
-        bf[ks][i] = *reinterpret_cast<const bf16x8*>(Bs(cur) + rb_ * kRowBytes + ((chunk ^ (rb_ & 7)) << 4));
-      }
-    }
-  };
-  auto mfmas = [&](const bf16x8 (&af)[2][4], const bf16x8 (&bf)[2][4]) {
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[ks][j], af[ks][i], acc[i][j], 0, 0, 0);
-  };
-
-  if constexpr (GLDS) {
-    // LDS-DMA staging (k_gemm_nt_glds): lane-linear LDS image, the (row & 7) chunk swizzle on
-    // the source address.  Rows past the expert's end / past N re-read the last valid row
-    // (their outputs are never stored), so nothing outside the expert's rows is touched.
-    const int lrow = lane >> 3, pchunk = lane & 7;
-    auto issue = [&](int k0, int buf) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int q = wave * 4 + i;
-        const int r = q * 8 + lrow;
-        const int c = pchunk ^ (r & 7);
-        const int ga = min(bm + r, row_end - 1), gb = min(bn + pair_perm(r), a.N - 1);
-        __builtin_amdgcn_global_load_lds((const void*)(a.A + (size_t)ga * a.lda + k0 + c * 8),
-                                         (__attribute__((address_space(3))) void*)(As(buf) + q * 1024), 16, 0, 0);
-        __builtin_amdgcn_global_load_lds((const void*)(Bg + (size_t)gb * a.ldb + k0 + c * 8),
-                                         (__attribute__((address_space(3))) void*)(Bs(buf) + q * 1024), 16, 0, 0);
-      }
-    };
-    const int nk = a.K / BK;
-    if (nk > 0) issue(0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    for (int kt = 0; kt < nk; ++kt) {
-      const int cur = kt & 1;
-      bf16x8 af[2][4], bf[2][4];
-      read_frags(cur, af, bf);  // every fragment read before the next tile's DMA is issued
-      if (kt + 1 < nk) issue((kt + 1) * BK, cur ^ 1);
-      __builtin_amdgcn_s_setprio(1);
-      mfmas(af, bf);
-      __builtin_amdgcn_s_setprio(0);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-    }
-  } else {
-    // register staging (k_gemm_nt): rows past the expert's end, rows past N and the K tail
-    // are zero-filled
-    uint4 ra[4], rb[4];
-    const int srow = t >> 3, schunk = t & 7;
-    auto gload = [&](int k0) {
-      const int gk = k0 + schunk * 8;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int r = srow + 32 * i;
-        const int gm = bm + r, gn = bn + pair_perm(r);
-        ra[i] = (gm < row_end && gk < a.K) ? *reinterpret_cast<const uint4*>(a.A + (size_t)gm * a.lda + gk) : uint4{0, 0, 0, 0};
-        rb[i] = (gn < a.N && gk < a.K) ? *reinterpret_cast<const uint4*>(Bg + (size_t)gn * a.ldb + gk) : uint4{0, 0, 0, 0};
-      }
-    };
-    auto swrite = [&](int buf) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int r = srow + 32 * i;
-        const int o = r * kRowBytes + ((schunk ^ (r & 7)) << 4);
-        *reinterpret_cast<uint4*>(As(buf) + o) = ra[i];
-        *reinterpret_cast<uint4*>(Bs(buf) + o) = rb[i];
-      }
-    };
-    const int nk = (a.K + BK - 1) / BK;
-    if (nk > 0) {
-      gload(0);
-      swrite(0);
-    }
-    __syncthreads();
-    for (int kt = 0; kt < nk; ++kt) {
-      const int cur = kt & 1;
-      if (kt + 1 < nk) gload((kt + 1) * BK);
-      bf16x8 af[2][4], bf[2][4];
-      read_frags(cur, af, bf);
-      mfmas(af, bf);
-      if (kt + 1 < nk) swrite(cur ^ 1);
-      __syncthreads();
-    }
-  }
-
-  // direct epilogue: acc[i][2p + h][r] = C[bm + wm + 16i + (lane & 15)][bn + wn + 32p + 8 (lane >> 4) + 4h + r],
-  // eight consecutive columns of one row per lane and pair; rows past the expert's end are masked
-  const int c = lane & 15, gq = lane >> 4;
-#pragma unroll
-  for (int p = 0; p < 2; ++p) {
-    const int col = bn + wn + 32 * p + 8 * gq;
-    float bias[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) bias[e] = 0.f;
-    if (a.bias_kind == 1 && col < a.N) {
-      const float* b = reinterpret_cast<const float*>(a.bias) + (size_t)g * a.bias_ld + col;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) bias[e] = b[e];
-    } else if (a.bias_kind == 2 && col < a.N) {
-      const uint16_t* b = reinterpret_cast<const uint16_t*>(a.bias) + (size_t)g * a.bias_ld + col;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) bias[e] = bf2f(b[e]);
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int row = bm + wm + 16 * i + c;
-      float v[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) v[e] = a.alpha * acc[i][2 * p + (e >> 2)][e & 3] + bias[e];
-      if (row < row_end && col < a.N) {
-        if constexpr (OUT_BF16) {
-          uint32_t w[4];
-#pragma unroll
-          for (int q = 0; q < 4; ++q) w[q] = pk_bf16(v[2 * q], v[2 * q + 1]);
-          *reinterpret_cast<uint4*>(reinterpret_cast<uint16_t*>(a.C) + (size_t)row * a.ldc + col) =
-              uint4{w[0], w[1], w[2], w[3]};
-        } else {
-          float4* C = reinterpret_cast<float4*>(reinterpret_cast<float*>(a.C) + (size_t)row * a.ldc + col);
-          C[0] = make_float4(v[0], v[1], v[2], v[3]);
-          C[1] = make_float4(v[4], v[5], v[6], v[7]);
-        }
-      }
-    }
-  }
+  const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
+  const void* bias = nullptr;  // bias[g]
+  if (a.bias_kind) bias = reinterpret_cast<const char*>(a.bias) + (size_t)g * a.bias_ld * (a.bias_kind == 1 ? 4 : 2);
+  const TileDst dst{a.C, a.ldc, row_end, a.N, a.alpha, bias, a.bias_kind};
+  store_direct_fast<OUT_BF16>(dst, acc, bm + wm, bn + wn, lane);
 }
 
 // ---------------------------------------------------------------------------
 // weight gradient: dw[g][N][K] = alpha * dy[rows of g]^T . x[rows of g]
-// (k_gemm_tn's PF = 2 form: 64-row tiles of both operands staged as they are, MFMA operands
+// (tn_loop_pf2: 64-row tiles of both operands staged as they are, MFMA operands
 // through ds_read_b64_tr_b16, two tiles in flight in two register sets)
 // ---------------------------------------------------------------------------
-typedef short v4s __attribute__((ext_vector_type(4)));
-typedef short v8s __attribute__((ext_vector_type(8)));
-constexpr int kTnRow = 288;           // bytes per LDS row (256 data + 32 pad)
-constexpr int kTnTile = BK * kTnRow;  // one operand tile
-
-__device__ __forceinline__ int tn_off(int row, int byte) { return row * kTnRow + (byte ^ (((row >> 3) & 1) << 7)); }
-
 __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) k_grouped_gemm_tn(GroupedArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[4 * kTnTile];
   __shared__ long long ws[4];
   __shared__ int seg[2];
-  const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+  const int t = threadIdx.x;
   // C rows = N (columns of dy), C columns = K (columns of x); the reduction runs over rows
   const int tiles_n = (a.K + BN - 1) / BN, tiles_m = (a.N + BM - 1) / BM;
   const int per = tiles_n * tiles_m;
@@ -321,109 +176,24 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) k_
   }
   const int off = __builtin_amdgcn_readfirstlane(seg[0]);
   const int rows = __builtin_amdgcn_readfirstlane(seg[1]) - off;
-  const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
-  auto As = [&](int buf) { return smem + buf * (2 * kTnTile); };
-  auto Bs = [&](int buf) { return smem + buf * (2 * kTnTile) + kTnTile; };
 
   floatx4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = floatx4{0.f, 0.f, 0.f, 0.f};
-
-  constexpr int PF = 2;
-  uint4 ra[PF][4], rb[PF][4];
-  const int schunk = t & 15, srow = t >> 4;
-  const int nk = (rows + BK - 1) / BK;
   // The mask is the buffer resource: it starts at the expert's first row and ends with the
   // last element of its last row, so rows past the expert's end (the next expert's, spare
   // rows, whatever they hold) load as zero and contribute exactly nothing.  Columns past
   // N / K read the row's neighbours inside the expert, or zero on its last row; they only
   // reach outputs that are never stored.
+  const uint16_t* Ag = a.A + (size_t)off * a.lda;
+  const uint16_t* Bg = a.B + (size_t)off * a.ldb;
   const uint32_t bytes_a = rows > 0 ? (uint32_t)(((size_t)(rows - 1) * a.lda + a.N) * 2) : 0u;
   const uint32_t bytes_b = rows > 0 ? (uint32_t)(((size_t)(rows - 1) * a.ldb + a.K) * 2) : 0u;
-  const Rsrc rsa = make_rsrc(uniform_ptr(reinterpret_cast<char*>(const_cast<uint16_t*>(a.A + (size_t)off * a.lda))), bytes_a);
-  const Rsrc rsb = make_rsrc(uniform_ptr(reinterpret_cast<char*>(const_cast<uint16_t*>(a.B + (size_t)off * a.ldb))), bytes_b);
-  auto gload = [&](int s, int m0) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const uint32_t m = (uint32_t)(m0 + srow + 16 * i);
-      const int ca = bm + schunk * 8, cb = bn + schunk * 8;
-      ra[s][i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rsa.r, (m * a.lda + ca) * 2, 0, 0));
-      rb[s][i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rsb.r, (m * a.ldb + cb) * 2, 0, 0));
-    }
-  };
-  auto swrite = [&](int buf, int s) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int r = srow + 16 * i;
-      *reinterpret_cast<uint4*>(As(buf) + tn_off(r, schunk * 16)) = ra[s][i];
-      *reinterpret_cast<uint4*>(Bs(buf) + tn_off(r, schunk * 16)) = rb[s][i];
-    }
-  };
-  const int grp = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
-  const int lrow = (grp * 8 + q) * kTnRow, xsw = (grp & 1) << 7;
-  const int la = lrow + ((wm * 2) ^ xsw) + 8 * p, lb = lrow + ((wn * 2) ^ xsw) + 8 * p;
-  auto compute = [&](int cur) {
-    const unsigned char* abase = As(cur) + la;
-    const unsigned char* bbase = Bs(cur) + lb;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      bf16x8 af[4], bf[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int o = ks * 32 * kTnRow + 32 * i;
-        const v4s a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s*)(abase + o));
-        const v4s a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s*)(abase + o + 4 * kTnRow));
-        const v4s b0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s*)(bbase + o));
-        const v4s b1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s*)(bbase + o + 4 * kTnRow));
-        af[i] = __builtin_bit_cast(bf16x8, (v8s)__builtin_shufflevector(a0, a1, 0, 1, 2, 3, 4, 5, 6, 7));
-        bf[i] = __builtin_bit_cast(bf16x8, (v8s)__builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7));
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bf[j], acc[i][j], 0, 0, 0);
-    }
-  };
-  // tile j goes to register set j % 2 and LDS buffer j & 1 one step before its MFMAs
-#pragma unroll
-  for (int u = 0; u < PF; ++u)
-    if (u < nk) gload(u, u * BK);
-  if (nk > 0) swrite(0, 0);
-  __syncthreads();
-  if (PF < nk) gload(0, PF * BK);
-  for (int kt = 0; kt < nk; kt += PF) {
-#pragma unroll
-    for (int u = 0; u < PF; ++u) {
-      if (kt + u < nk) {
-        compute(u & 1);
-        if (kt + u + 1 < nk) swrite((u + 1) & 1, (u + 1) % PF);
-        __syncthreads();
-        if (kt + u + 1 + PF < nk) gload((u + 1) % PF, (kt + u + 1 + PF) * BK);
-      }
-    }
-  }
+  const Rsrc rsa = make_rsrc(uniform_ptr(reinterpret_cast<char*>(const_cast<uint16_t*>(Ag))), bytes_a);
+  const Rsrc rsb = make_rsrc(uniform_ptr(reinterpret_cast<char*>(const_cast<uint16_t*>(Bg))), bytes_b);
+  tn_loop_pf2(rsa, rsb, a.lda, a.ldb, bm, bn, (rows + BK - 1) / BK, smem, acc, t);
   __syncthreads();
   // LDS-staged fp32 rows (the operand buffers are dead): an expert with no rows stores zeros
-  float* tile = reinterpret_cast<float*>(smem);
-  constexpr int TS = BN + 4;
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        tile[(wm + i * 16 + (lane >> 4) * 4 + r) * TS + wn + j * 16 + (lane & 15)] = a.alpha * acc[i][j][r];
-  __syncthreads();
   float* Cg = reinterpret_cast<float*>(a.C) + (size_t)g * a.c_stride;
-  for (int idx = t; idx < BM * (BN / 4); idx += NT) {
-    const int rl = idx / (BN / 4), cl = (idx % (BN / 4)) * 4;
-    const int row = bm + rl, col = bn + cl;
-    if (row >= a.N || col >= a.K) continue;
-    *reinterpret_cast<float4*>(Cg + (size_t)row * a.ldc + col) =
-        make_float4(tile[rl * TS + cl], tile[rl * TS + cl + 1], tile[rl * TS + cl + 2], tile[rl * TS + cl + 3]);
-  }
+  store_tile_f32<false, false>(TileDst{Cg, a.ldc, a.N, a.K, a.alpha, nullptr, 0}, acc, smem, bm, bn, t);
 }
 
 void check_common(const char* op, uint64_t A, uint64_t B, uint64_t C, uint64_t counts, int cap, int N, int K, int G,

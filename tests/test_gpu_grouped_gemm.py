@@ -2,7 +2,9 @@
 ``x[rows].float() @ w[g].float().T`` loop in torch: forward in both output dtypes with
 sentinel rows, isolation of an expert from the others (bitwise), counts that overflow the
 buffer, int32 / int64 counts, the weight gradient with NaN outside the expert's rows,
-``grouped_linear`` against torch autograd, and a captured graph replayed with new counts.
+``grouped_linear`` against torch autograd, a captured graph replayed with new counts, and
+a single expert that owns every row against the dense 128x128 kernels (bitwise: both run
+the tile of csrc/device/gemm_tile128.hpp).
 
 Tolerances are those of tests/test_gpu_kernels.py for the same tile and randn inputs:
 fp32 forward rtol 2e-3, atol 2e-3 sqrt(K); bf16 forward rtol 2e-2, atol 8e-2; weight
@@ -126,6 +128,40 @@ def test_isolation(name, out_dtype):
             continue
         alone = grouped_gemm_nt(x[a:b], w[g:g + 1], _cnt([b - a]), out_dtype=out_dtype)
         assert torch.equal(alone, full[a:b]), f"expert {g} differs from a G = 1 call on its slice"
+
+
+def test_single_expert_is_the_dense_128_tile_bit_for_bit():
+    """One expert that owns every row runs the dense 128x128 kernel's loop on the same
+    operand order (csrc/device/gemm_tile128.hpp), so the results are equal bit for bit.
+    Forward at K % 64 == 0 only: for other K the dense kernel uses the unpermuted
+    staged-epilogue form by design."""
+    from collective_communication_mpi_amd import _native
+    from collective_communication_mpi_amd.ops import gemm_nt, gemm_tn, grouped_gemm_nt, grouped_gemm_tn
+
+    D = _native.device()
+    g = torch.Generator(device="cuda").manual_seed(128128)
+    D.gemm_set_kernel(1)
+    try:
+        # two row tiles and two column tiles with masked tails; an even and an odd number of K tiles
+        for cap, N, K in [(200, 136, 128), (200, 136, 192)]:
+            x = torch.randn(cap, K, device="cuda", generator=g).bfloat16()
+            w = torch.randn(N, K, device="cuda", generator=g).bfloat16()
+            for dt in (torch.float32, torch.bfloat16):
+                got = grouped_gemm_nt(x, w[None], _cnt([cap]), out_dtype=dt)
+                assert torch.equal(got, gemm_nt(x, w, out_dtype=dt)), f"forward {(cap, N, K)} {dt}"
+        bias = torch.randn(N, device="cuda", generator=g)
+        got = grouped_gemm_nt(x, w[None], _cnt([cap]), bias=bias[None], out_dtype=torch.float32)
+        assert torch.equal(got, gemm_nt(x, w, bias=bias, out_dtype=torch.float32)), "forward with an fp32 bias"
+        D.gemm_tn_set_prefetch(2)
+        # 4 row tiles, the last with 8 valid rows; 5 tiles, an odd count for the two-in-flight loop
+        for rows, N, K in [(200, 136, 72), (320, 128, 72)]:
+            dy = torch.randn(rows, N, device="cuda", generator=g).bfloat16()
+            x = torch.randn(rows, K, device="cuda", generator=g).bfloat16()
+            got = grouped_gemm_tn(dy, x, _cnt([rows]))[0]
+            assert torch.equal(got, gemm_tn(dy, x, splitk=1)), f"weight gradient {(rows, N, K)}"
+    finally:
+        D.gemm_tn_set_prefetch(0)
+        D.gemm_set_kernel(0)
 
 
 def test_overflow():
