@@ -200,6 +200,10 @@ __device__ __forceinline__ void acquire_sys() {
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ float bf16_lo(uint32_t w) { return __uint_as_float(w << 16); }
 __device__ __forceinline__ float bf16_hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
+// the sigmoid of the SwiGLU kernels and of the GEMM epilogues that apply the gate
+__device__ __forceinline__ float sigmoid_fast(float x) {
+  return __builtin_amdgcn_rcpf(1.0f + __expf(-x));  // exp -> inf gives 0, exp -> 0 gives 1
+}
 // fp32 -> bf16 bits, round to nearest even, NaN stays NaN: gfx950's v_cvt_pk_bf16_f32 (one
 // VALU op; the integer RNE sequence it replaces compiled to an exec-mask branch per value for
 // its NaN test).  Denormals are preserved (the kernels' fp32 denorm mode).

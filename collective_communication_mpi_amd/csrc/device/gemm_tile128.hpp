@@ -44,6 +44,8 @@ struct TileDst {
   float alpha;
   const void* bias;  // [col_end] fp32 / bf16, null without a bias
   int bias_kind;     // 0 none, 1 fp32, 2 bf16
+  void* glu = nullptr;  // store_direct_fast<true, true>: [row_end][col_end / 2] bf16 SwiGLU gate of C's column pairs
+  int ldg = 0;
 };
 
 __device__ __forceinline__ void zero_acc(floatx4 (&acc)[4][4]) {
@@ -324,6 +326,119 @@ __device__ __forceinline__ void tn_loop_pf2(Rsrc rsa, Rsrc rsb, int lda, int ldb
 }
 
 // ---------------------------------------------------------------------------
+// NN loop: acc = A[bm.., reduction range] . B[reduction range, bn..], A contiguous in the
+// reduction (as in the NT loops), B row-major with the reduction over its rows (as in the
+// TN tile).  A is staged in the NT image (LDS-DMA for GLDS, which needs a reduction length
+// that is a multiple of 64; through registers with a zero-filled tail otherwise), B's 64
+// reduction rows x 128 columns are staged as they are in the TN image and read through
+// ds_read_b64_tr_b16 with tn_compute's addresses.  Both fragments are the standard
+// 16x16x32 operand (index lane & 15, reduction elements 8 * (lane >> 4) .. + 7), so they
+// meet in one MFMA; the operands are swapped (B first), which leaves every lane 4
+// consecutive columns of one row: acc[i][j][r] = C[bm + wm + 16 i + (lane & 15)]
+// [bn + wn + 16 j + 4 * (lane >> 4) + r] (store_direct4).
+// B is read through the buffer resource rsb, which starts at B's first reduction row and
+// ends with the last element of its last one: rows past the reduction load as zero with no
+// branch, so whatever lies behind them never reaches an MFMA (A's side of the tail is
+// zero-filled too, so the tail is 0 * 0).  Columns past B's width read the row's
+// neighbours, which only reach outputs that are never stored.  Every lane runs every
+// transposing read (it needs EXEC all ones); only the A loads of the register-staged
+// form are predicated.
+// ---------------------------------------------------------------------------
+constexpr int kNnABytes = BM * kRowBytes;                     // one A buffer (NT image)
+constexpr int kNnLoopBytes = 2 * kNnABytes + 2 * kTnTile;     // two A + two B buffers
+__device__ __forceinline__ unsigned char* nn_as(unsigned char* smem, int buf) { return smem + buf * kNnABytes; }
+__device__ __forceinline__ unsigned char* nn_bs(unsigned char* smem, int buf) { return smem + 2 * kNnABytes + buf * kTnTile; }
+
+// s: A, lda, bm, a_end, K = reduction length, nk = its BK tiles (B, ldb, b_end and kt0 are
+// not used: B comes through rsb, row stride ldb elements, first column bn)
+template <bool GLDS>
+__device__ __forceinline__ void nn_loop(const NtSrc& s, Rsrc rsb, unsigned char* smem, floatx4 (&acc)[4][4], int wave,
+                                        int t) {
+  const int lane = t & 63;
+  const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
+  const NtFragOff fo = nt_frag_off(wm, wn, lane);
+  // B fragment addresses: tn_compute's (bank-conflict free in this pattern only)
+  const int grp = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
+  const int lb = (grp * 8 + q) * kTnRow + ((wn * 2) ^ ((grp & 1) << 7)) + 8 * p;
+  uint4 ra[GLDS ? 1 : 4], rb[4];
+  const int brow = t >> 4, bchunk = t & 15;  // B staging: rows brow + 16 i, 16-B chunk bchunk
+  const int arow = t >> 3, achunk = t & 7;   // A register staging: rows arow + 32 i, chunk achunk
+  const int lrow = lane >> 3, pchunk = lane & 7;
+  auto gload_b = [&](int kt) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const uint32_t n = (uint32_t)(kt * BK + brow + 16 * i);
+      rb[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rsb.r, (n * s.ldb + s.bn + bchunk * 8) * 2, 0, 0));
+    }
+  };
+  auto load_a = [&](int kt, int buf) {
+    if constexpr (GLDS) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int c16 = wave * 4 + i;  // 1 KiB LDS chunk = rows c16 * 8 .. + 7
+        const int r = c16 * 8 + lrow;
+        const int c = pchunk ^ (r & 7);
+        const int ga = min(s.bm + r, s.a_end - 1);
+        __builtin_amdgcn_global_load_lds((const void*)(s.A + (size_t)ga * s.lda + kt * BK + c * 8),
+                                         (__attribute__((address_space(3))) void*)(nn_as(smem, buf) + c16 * 1024), 16, 0, 0);
+      }
+    } else {
+      const int gk = kt * BK + achunk * 8;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int gm = s.bm + arow + 32 * i;
+        ra[i] = (gm < s.a_end && gk < s.K) ? *reinterpret_cast<const uint4*>(s.A + (size_t)gm * s.lda + gk) : uint4{0, 0, 0, 0};
+      }
+    }
+  };
+  auto swrite = [&](int buf) {
+    if constexpr (!GLDS) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int r = arow + 32 * i;
+        *reinterpret_cast<uint4*>(nn_as(smem, buf) + r * kRowBytes + ((achunk ^ (r & 7)) << 4)) = ra[i];
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) *reinterpret_cast<uint4*>(nn_bs(smem, buf) + tn_off(brow + 16 * i, bchunk * 16)) = rb[i];
+  };
+  zero_acc(acc);
+  if (s.nk <= 0) return;  // workgroup-uniform
+  load_a(0, 0);
+  gload_b(0);
+  swrite(0);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  for (int kt = 0; kt < s.nk; ++kt) {
+    const int cur = kt & 1;
+    // every fragment read of this tile before the next tile's loads are issued (see nt_loop_glds)
+    bf16x8 af[2][4], bf[2][4];
+    const unsigned char* abase = nn_as(smem, cur);
+    const unsigned char* bbase = nn_bs(smem, cur) + lb;
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        af[ks][i] = *reinterpret_cast<const bf16x8*>(abase + fo.a[ks] + i * 16 * kRowBytes);
+        const int o = ks * 32 * kTnRow + 32 * i;
+        const v4s b0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s*)(bbase + o));
+        const v4s b1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s*)(bbase + o + 4 * kTnRow));
+        bf[ks][i] = __builtin_bit_cast(bf16x8, (v8s)__builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7));
+      }
+    if (kt + 1 < s.nk) {
+      load_a(kt + 1, cur ^ 1);
+      gload_b(kt + 1);
+    }
+    __builtin_amdgcn_s_setprio(1);
+    nt_mfmas<true>(af, bf, acc);
+    __builtin_amdgcn_s_setprio(0);
+    if (kt + 1 < s.nk) swrite(cur ^ 1);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+  }
+}
+
+// ---------------------------------------------------------------------------
 // epilogues on a destination described by values
 // ---------------------------------------------------------------------------
 
@@ -333,7 +448,10 @@ __device__ __forceinline__ void tn_loop_pf2(Rsrc rsa, Rsrc rsb, int lda, int ldb
 // where the caller passes a constant (the dense kernels).  The rest is straight-line
 // code (the generic store_direct of gemm.hip unrolls every runtime combination into ~12k
 // instructions).  row0 / col0: the wave's first row / column.
-template <bool OUT_BF16>
+// GLU (bf16 output only): the lane's 8 columns are 4 whole (gate, up) pairs of an interleaved
+// gate|up output; their SwiGLU gate, computed from the bf16-rounded values as k_swiglu_fwd_il
+// computes it from memory, goes to d.glu[row][col / 2] as one 8-B vector.
+template <bool OUT_BF16, bool GLU = false>
 __device__ __forceinline__ void store_direct_fast(const TileDst& d, const floatx4 (&acc)[4][4], int row0, int col0,
                                                   int lane) {
   const int c = lane & 15, gq = lane >> 4;
@@ -364,11 +482,45 @@ __device__ __forceinline__ void store_direct_fast(const TileDst& d, const floatx
           for (int q = 0; q < 4; ++q) w[q] = pk_bf16(v[2 * q], v[2 * q + 1]);
           *reinterpret_cast<uint4*>(reinterpret_cast<uint16_t*>(d.C) + (size_t)row * d.ldc + col) =
               uint4{w[0], w[1], w[2], w[3]};
+          if constexpr (GLU) {
+            float a[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+              const float gv = bf16_lo(w[q]);
+              a[q] = gv * sigmoid_fast(gv) * bf16_hi(w[q]);
+            }
+            *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(d.glu) + (size_t)row * d.ldg + (col >> 1)) =
+                uint2{pk_bf16(a[0], a[1]), pk_bf16(a[2], a[3])};
+          }
         } else {
           float4* C = reinterpret_cast<float4*>(reinterpret_cast<float*>(d.C) + (size_t)row * d.ldc + col);
           C[0] = make_float4(v[0], v[1], v[2], v[3]);
           C[1] = make_float4(v[4], v[5], v[6], v[7]);
         }
+      }
+    }
+  }
+}
+
+// Direct epilogue of nn_loop (alpha only): 4 consecutive columns of one row per lane and
+// MFMA tile, one 8-B (bf16) or 16-B (fp32) vector store each; col_end % 4 == 0.
+template <bool OUT_BF16>
+__device__ __forceinline__ void store_direct4(const TileDst& d, const floatx4 (&acc)[4][4], int row0, int col0, int lane) {
+  const int c = lane & 15, gq = lane >> 4;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int row = row0 + 16 * i + c;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int col = col0 + 16 * j + 4 * gq;
+      if (row < d.row_end && col < d.col_end) {
+        const float v0 = d.alpha * acc[i][j][0], v1 = d.alpha * acc[i][j][1], v2 = d.alpha * acc[i][j][2],
+                    v3 = d.alpha * acc[i][j][3];
+        if constexpr (OUT_BF16)
+          *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(d.C) + (size_t)row * d.ldc + col) =
+              uint2{pk_bf16(v0, v1), pk_bf16(v2, v3)};
+        else
+          *reinterpret_cast<float4*>(reinterpret_cast<float*>(d.C) + (size_t)row * d.ldc + col) = make_float4(v0, v1, v2, v3);
       }
     }
   }

@@ -30,10 +30,6 @@ namespace dev {
 
 namespace {
 
-__device__ __forceinline__ float sigmoid_fast(float x) {
-  return __builtin_amdgcn_rcpf(1.0f + __expf(-x));  // exp -> inf gives 0, exp -> 0 gives 1
-}
-
 __device__ __forceinline__ uint32_t pack_bf16(float lo, float hi) {
   return pk_bf16(lo, hi);
 }

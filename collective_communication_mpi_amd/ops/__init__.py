@@ -16,6 +16,13 @@ from .kernels import (  # noqa: F401
     deinterleave_lastaxis,
     grouped_gemm_nt,
     grouped_gemm_tn,
+    grouped_gemm_nn,
+    grouped_gemm_nt_swiglu,
+    grouped_nn_validate,
+    grouped_dx,
+    grouped_dx_route,
+    grouped_grad_rows,
+    grouped_swiglu_route,
     grouped_linear,
     grouped_validate,
     grouped_tile_map,

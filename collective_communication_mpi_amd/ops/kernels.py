@@ -459,6 +459,100 @@ def grouped_gemm_tn(dy: torch.Tensor, x: torch.Tensor, counts: torch.Tensor, out
     return out
 
 
+def grouped_nn_validate(dy, w, counts, out=None, out_dtype=torch.bfloat16):
+    """Argument rules of ``grouped_gemm_nn`` that need no GPU; raises TypeError (dtypes) /
+    ValueError (shapes, strides, bounds) and returns ``(cap, G, N, K)``.  ``dy`` is
+    ``[cap, N]`` and ``w`` is ``[G, N, K]`` exactly as ``grouped_gemm_nt`` takes it: unit inner
+    strides, row and expert strides free multiples of 8 elements."""
+    if dy.dtype != torch.bfloat16 or w.dtype != torch.bfloat16:
+        raise TypeError("grouped_gemm_nn expects bf16 operands")
+    if dy.dim() != 2 or w.dim() != 3 or dy.shape[1] != w.shape[1]:
+        raise ValueError(f"grouped_gemm_nn shape mismatch: dy {tuple(dy.shape)}, w {tuple(w.shape)} "
+                         "(want [cap, N], [G, N, K])")
+    cap, N = dy.shape
+    G, K = w.shape[0], w.shape[2]
+    if G < 1 or G > GROUPED_MAX_EXPERTS:
+        raise ValueError(f"grouped_gemm_nn: the number of experts must be in [1, {GROUPED_MAX_EXPERTS}], got {G}")
+    if K < 8 or N < 8 or K % 8 or N % 8:
+        raise ValueError(f"grouped_gemm_nn: N ({N}) and K ({K}) must be positive multiples of 8")
+    if dy.stride(1) != 1 or w.stride(2) != 1:
+        raise ValueError("grouped_gemm_nn operands must have unit inner stride")
+    if (cap > 1 and dy.stride(0) % 8) or w.stride(1) % 8 or (G > 1 and w.stride(0) % 8):
+        raise ValueError("grouped_gemm_nn: row and expert strides must be multiples of 8 elements (16 bytes)")
+    if w.stride(1) < K:
+        raise ValueError("grouped_gemm_nn: the rows of w must not overlap")
+    if dy.data_ptr() % 16 or w.data_ptr() % 16:
+        raise ValueError("grouped_gemm_nn: operands must be 16-B aligned")
+    if counts.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"grouped_gemm_nn: counts must be int32 or int64, got {counts.dtype}")
+    if counts.dim() != 1 or counts.shape[0] != G or not counts.is_contiguous():
+        raise ValueError(f"grouped_gemm_nn: counts must be a contiguous [{G}] tensor, got {tuple(counts.shape)}")
+    if counts.device != dy.device or w.device != dy.device:
+        raise ValueError("grouped_gemm_nn: dy, w and counts must be on the same device")
+    if out is not None:
+        if out.dtype not in (torch.bfloat16, torch.float32):
+            raise TypeError("grouped_gemm_nn output must be bf16 or fp32")
+        if out.shape != (cap, K) or out.stride(1) != 1 or out.device != dy.device:
+            raise ValueError("grouped_gemm_nn output must be [cap, K] with unit column stride on dy's device")
+        if out.data_ptr() % 16 or (cap > 1 and (out.stride(0) * out.element_size()) % 16):
+            raise ValueError("grouped_gemm_nn output rows must be 16-B aligned")
+    elif out_dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError("grouped_gemm_nn output must be bf16 or fp32")
+    return int(cap), int(G), int(N), int(K)
+
+
+def grouped_gemm_nn(dy: torch.Tensor, w: torch.Tensor, counts: torch.Tensor, out: Optional[torch.Tensor] = None,
+                    alpha: float = 1.0, out_dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+    """Input gradient of ``grouped_gemm_nt``: ``out[r] = alpha * dy[r] @ w[g]`` for every row r
+    of expert g, with ``w`` [G, N, K] read as the forward takes it (no transposed copy): the
+    kernel stages 64 reduction rows x 128 columns of ``w[g]`` as they lie and reads its MFMA
+    operand through ds_read_b64_tr_b16.
+
+    dy: [cap, N] bf16 (row stride free), counts: [G] int32 / int64 on the device, out:
+    [cap, K] bf16 or fp32.  The row rules are ``grouped_gemm_nt``'s: no host synchronisation,
+    a grid sized from cap, G and K alone, rows at or past ``sum(c_g)`` left untouched.  The
+    reduction stops at N exactly: what lies past column N of a strided ``dy`` or past row N of
+    ``w[g]`` (the next expert, the end of the allocation) never reaches a result."""
+    cap, G, N, K = grouped_nn_validate(dy, w, counts, out, out_dtype)
+    if out is None:
+        out = torch.empty((cap, K), dtype=out_dtype, device=dy.device)
+    _D().grouped_gemm_nn(dy.data_ptr(), w.data_ptr(), out.data_ptr(), counts.data_ptr(), cap, N, K, G,
+                         dy.stride(0) if cap > 1 else N, w.stride(1), w.stride(0), out.stride(0) if cap > 1 else K,
+                         float(alpha), out.dtype == torch.bfloat16, counts.dtype == torch.int64, _stream(dy))
+    return out
+
+
+def grouped_gemm_nt_swiglu(x: torch.Tensor, w: torch.Tensor, counts: torch.Tensor, h: Optional[torch.Tensor] = None,
+                           glu: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
+                           alpha: float = 1.0):
+    """``grouped_gemm_nt`` of an interleaved gate|up weight with the SwiGLU gate in its
+    epilogue: returns ``(h, glu)``, ``h`` [cap, N] bf16 exactly what ``grouped_gemm_nt(x, w,
+    counts, bias=bias, alpha=alpha)`` writes and ``glu[r, j] = silu(h[r, 2j]) * h[r, 2j + 1]``
+    ([cap, N / 2] bf16, bit for bit ``swiglu_pairs(h)``), written by the same kernel for the
+    same rows.  Rows at or past ``sum(counts)`` of both outputs are left untouched."""
+    cap, G, N, K = grouped_validate(x, w, counts, h, bias, torch.bfloat16)
+    if h is not None and h.dtype != torch.bfloat16:
+        raise TypeError("grouped_gemm_nt_swiglu: h must be bf16")
+    if glu is not None:
+        if glu.dtype != torch.bfloat16:
+            raise TypeError("grouped_gemm_nt_swiglu: glu must be bf16")
+        if glu.shape != (cap, N // 2) or glu.stride(1) != 1 or glu.device != x.device:
+            raise ValueError("grouped_gemm_nt_swiglu: glu must be [cap, N / 2] with unit column stride on x's device")
+        if glu.data_ptr() % 8 or (cap > 1 and glu.stride(0) % 4):
+            raise ValueError("grouped_gemm_nt_swiglu: glu rows must be 8-B aligned")
+    if h is None:
+        h = torch.empty((cap, N), dtype=torch.bfloat16, device=x.device)
+    if glu is None:
+        glu = torch.empty((cap, N // 2), dtype=torch.bfloat16, device=x.device)
+    bias_kind = 0 if bias is None else (1 if bias.dtype == torch.float32 else 2)
+    _D().grouped_gemm_nt_swiglu(x.data_ptr(), w.data_ptr(), h.data_ptr(), glu.data_ptr(),
+                                0 if bias is None else bias.data_ptr(), counts.data_ptr(), cap, N, K, G,
+                                x.stride(0) if cap > 1 else K, w.stride(1), w.stride(0),
+                                h.stride(0) if cap > 1 else N, glu.stride(0) if cap > 1 else N // 2, N, float(alpha),
+                                bias_kind, counts.dtype == torch.int64, _stream(x))
+    return h, glu
+
+
 def _transposed_experts(w: torch.Tensor) -> torch.Tensor:
     """``[G, K, N]`` view of one transposed copy of ``w`` [G, N, K]: the existing 2-D transpose
     kernel turns the [G * N, K] matrix into [K, G * N]; expert g's w[g].T is its column block
@@ -466,6 +560,40 @@ def _transposed_experts(w: torch.Tensor) -> torch.Tensor:
     G, N, K = w.shape
     wt = transpose(w.contiguous().view(G * N, K))
     return wt.view(K, G, N).permute(1, 0, 2)
+
+
+def grouped_dx_route() -> str:
+    """How ``grouped_linear`` and ``GroupedExpertsMLP`` compute dX, read from the environment at
+    call time: ``"nn"`` (default, ``grouped_gemm_nn`` on the weights as they lie) or
+    ``"transpose"`` (``CCMPI_GROUPED_DX=transpose``: ``grouped_gemm_nt`` on a transposed copy
+    of every expert's weights, kept for A/B runs)."""
+    v = os.environ.get("CCMPI_GROUPED_DX", "nn")
+    if v not in ("nn", "transpose"):
+        raise ValueError(f"CCMPI_GROUPED_DX must be 'nn' or 'transpose', got {v!r}")
+    return v
+
+
+def grouped_swiglu_route() -> str:
+    """How ``GroupedExpertsMLP`` applies the gate, read from the environment at call time:
+    ``"fused"`` (default, ``grouped_gemm_nt_swiglu``) or ``"unfused"``
+    (``CCMPI_GROUPED_SWIGLU=unfused``: ``grouped_linear``, ``swiglu_pairs``, ``grouped_linear``)."""
+    v = os.environ.get("CCMPI_GROUPED_SWIGLU", "fused")
+    if v not in ("fused", "unfused"):
+        raise ValueError(f"CCMPI_GROUPED_SWIGLU must be 'fused' or 'unfused', got {v!r}")
+    return v
+
+
+def grouped_grad_rows(dy: torch.Tensor) -> torch.Tensor:
+    """``dy`` as the grouped backward kernels read it (unit inner stride, 16-B aligned rows)."""
+    ok = dy.stride(1) == 1 and (dy.shape[0] <= 1 or dy.stride(0) % 8 == 0) and dy.data_ptr() % 16 == 0
+    return dy if ok else dy.contiguous()
+
+
+def grouped_dx(dy: torch.Tensor, wb: torch.Tensor, counts: torch.Tensor, out_dtype: torch.dtype) -> torch.Tensor:
+    """``dy . w[g]`` over the rows of every expert by the route ``grouped_dx_route`` names."""
+    if grouped_dx_route() == "transpose":
+        return grouped_gemm_nt(dy, _transposed_experts(wb), counts, out_dtype=out_dtype)
+    return grouped_gemm_nn(dy, wb, counts, out_dtype=out_dtype)
 
 
 class _GroupedLinear(torch.autograd.Function):
@@ -479,11 +607,10 @@ class _GroupedLinear(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, wb, counts = ctx.saved_tensors
-        ok = dy.stride(1) == 1 and (dy.shape[0] <= 1 or dy.stride(0) % 8 == 0) and dy.data_ptr() % 16 == 0
-        dy = dy if ok else dy.contiguous()
+        dy = grouped_grad_rows(dy)
         dx = dw = None
         if ctx.needs_input_grad[0]:
-            dx = grouped_gemm_nt(dy, _transposed_experts(wb), counts, out_dtype=x.dtype)
+            dx = grouped_dx(dy, wb, counts, x.dtype)
         if ctx.needs_input_grad[1]:
             dw = grouped_gemm_tn(dy, x, counts).to(ctx.w_dtype)
         return dx, dw, None
@@ -492,9 +619,10 @@ class _GroupedLinear(torch.autograd.Function):
 def grouped_linear(x: torch.Tensor, w: torch.Tensor, counts: torch.Tensor) -> torch.Tensor:
     """Differentiable ``grouped_gemm_nt(x, w, counts)`` (bf16 out).  ``w`` is bf16, or fp32
     master weights (rounded to bf16 for the kernels; their gradient then keeps the fp32 the
-    weight-gradient kernel computes).  Backward: dX is the forward kernel on a transposed copy
-    of the weights (one ``transpose`` launch over [G * N, K]; the kernel has no K-major-B
-    path), dW is ``grouped_gemm_tn`` in w's dtype; ``counts`` gets no gradient.  Neither
+    weight-gradient kernel computes).  Backward: dX is ``grouped_gemm_nn`` on the weights as
+    they lie (``CCMPI_GROUPED_DX=transpose``, read at call time, selects the earlier route: one
+    ``transpose`` launch over [G * N, K] and the forward kernel on the copy), dW is
+    ``grouped_gemm_tn`` in w's dtype; ``counts`` gets no gradient.  Neither
     direction synchronises with the host.  Like the forward's output, dX is written for the
     rows of the experts only: gradient rows at or past ``sum(counts)`` are unspecified
     (uninitialised memory), as are the output's."""
