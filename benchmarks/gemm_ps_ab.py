@@ -3,7 +3,7 @@
     python benchmarks/gemm_ps_ab.py [--rounds 5] [--scheds 8,16392]
 
 Variants (``gemm_set_ring_sched``: bit 3 the ring, bit 14 pair slots, bit 0 persistent
-grid, bit 15 long K on the ring too, bit 13 the whole-line ablation) and hipBLASLt
+grid, bit 15 long K on the ring too) and hipBLASLt
 (torch.matmul) are timed in interleaved rounds in one process (median of per-round
 medians), bf16 in / out, uniform random operands.  One JSON line per shape."""
 import argparse

@@ -37,8 +37,6 @@ namespace dev {
 namespace {
 using namespace gemm;
 
-bool g_use_glds = std::getenv("CCMPI_GEMM_NO_GLDS") == nullptr;  // A/B switch (benchmarks)
-bool g_direct_epi = std::getenv("CCMPI_GEMM_STAGED_EPI") == nullptr;  // LDS-free epilogue (A/B switch)
 // (round 1 also carried a BK = 32, a multi-stage (3-5 x 16 KiB) and a persistent
 // form of the 128x128 kernel; all measured slower or no faster
 // (profiles/r1_qkv_reassoc/qkv_shapes2.txt, profiles/r1_gemm_fastepi) and were removed)
@@ -90,41 +88,10 @@ __device__ __forceinline__ void store_direct(const GemmArgs& g, const floatx4 (&
       if (g.splitk > 1) {
         float* C = reinterpret_cast<float*>(g.C) + (size_t)row * g.ldc + col;
         for (int e = 0; e < 8 && col + e < g.N; ++e) atomicAdd(C + e, v[e]);
-      } else if (vec_ok && col + 8 <= g.N) {
-        if (g.out_bf16) {
-          uint16_t* C = reinterpret_cast<uint16_t*>(g.C) + (size_t)row * g.ldc + col;
-          if (g.accumulate) {
-            const uint4 o = *reinterpret_cast<const uint4*>(C);
-            const uint32_t ow[4] = {o.x, o.y, o.z, o.w};
-#pragma unroll
-            for (int q = 0; q < 4; ++q) { v[2 * q] += bf16_lo(ow[q]); v[2 * q + 1] += bf16_hi(ow[q]); }
-          }
-          uint32_t w[4];
-#pragma unroll
-          for (int q = 0; q < 4; ++q) w[q] = pk_bf16(v[2 * q], v[2 * q + 1]);
-          *reinterpret_cast<uint4*>(C) = uint4{w[0], w[1], w[2], w[3]};
-        } else {
-          float4* C = reinterpret_cast<float4*>(reinterpret_cast<float*>(g.C) + (size_t)row * g.ldc + col);
-          float4 o0 = make_float4(v[0], v[1], v[2], v[3]), o1 = make_float4(v[4], v[5], v[6], v[7]);
-          if (g.accumulate) {
-            const float4 p0 = C[0], p1 = C[1];
-            o0.x += p0.x; o0.y += p0.y; o0.z += p0.z; o0.w += p0.w;
-            o1.x += p1.x; o1.y += p1.y; o1.z += p1.z; o1.w += p1.w;
-          }
-          C[0] = o0;
-          C[1] = o1;
-        }
       } else {
-        for (int e = 0; e < 8 && col + e < g.N; ++e) {
-          const size_t o = (size_t)row * g.ldc + col + e;
-          if (g.out_bf16) {
-            uint16_t* C = reinterpret_cast<uint16_t*>(g.C);
-            C[o] = (uint16_t)f32_to_bf16_bits(v[e] + (g.accumulate ? bf2f(C[o]) : 0.f));
-          } else {
-            float* C = reinterpret_cast<float*>(g.C);
-            C[o] = v[e] + (g.accumulate ? C[o] : 0.f);
-          }
-        }
+        // per vector: only the group that crosses column N goes element by element
+        // (the four-wave kernels, gemm_w4.hip, decide once per tile instead)
+        store_row8(g, g.ldc, row, col, v, vec_ok && col + 8 <= g.N);
       }
     }
   }
@@ -160,15 +127,11 @@ __global__ void __launch_bounds__(NT) k_gemm_nt(GemmArgs g) {
 }
 
 // Same tile / wave layout as k_gemm_nt, staged by LDS-DMA (nt_loop_glds); used only
-// when K % 64 == 0.
-__constant__ int g_pp_exp_dev = 0;
-
-// DIRECT: swapped MFMA operands + pair-permuted B staging + LDS-free epilogue
-// (store_direct); otherwise the LDS-staged row epilogue (store_tile).
-template <bool DIRECT, int FAST = 0>  // FAST = 1 + out_bf16 + 2 * bias_kind (store_direct_fast), 0 = generic
+// when K % 64 == 0.  Swapped MFMA operands + pair-permuted B staging + LDS-free epilogue
+// (store_direct / store_direct_fast).
+template <int FAST>  // FAST = 1 + out_bf16 + 2 * bias_kind (store_direct_fast), 0 = generic
 __global__ void __launch_bounds__(NT) k_gemm_nt_glds(GemmArgs g) {
-  constexpr int kEpi = DIRECT ? 0 : kEpiBytes;
-  __shared__ __attribute__((aligned(16))) unsigned char smem[kNtLoopBytes > kEpi ? kNtLoopBytes : kEpi];
+  __shared__ __attribute__((aligned(16))) unsigned char smem[kNtLoopBytes];
   const int tiles_n = (g.N + BN - 1) / BN, tiles_m = (g.M + BM - 1) / BM;
   int wg = xcd_remap(blockIdx.x, tiles_n * tiles_m * g.splitk);
   const int split = wg % g.splitk;
@@ -181,21 +144,13 @@ __global__ void __launch_bounds__(NT) k_gemm_nt_glds(GemmArgs g) {
   floatx4 acc[4][4];
   int kt0, nk;
   split_tiles(g.K / BK, g.splitk, split, kt0, nk);
-  nt_loop_glds<DIRECT>(NtSrc{g.A, g.B, g.lda, g.ldb, bm, g.M, bn, g.N, g.K, kt0, nk}, smem, acc, wave, lane);
+  nt_loop_glds(NtSrc{g.A, g.B, g.lda, g.ldb, bm, g.M, bn, g.N, g.K, kt0, nk}, smem, acc, wave, lane);
 
-  if (g_pp_exp_dev & 8) {  // ablation (benchmarks only): no epilogue, accumulators kept live
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) asm volatile("" ::"v"(acc[i][j]));
-    return;
-  }
   constexpr bool kFastBf16 = ((FAST - 1) & 1) != 0;
   constexpr int kFastBias = (FAST - 1) / 2;
-  if constexpr (DIRECT && FAST > 0)
+  if constexpr (FAST > 0)
     store_direct_fast<kFastBf16>(TileDst{g.C, g.ldc, g.M, g.N, g.alpha, g.bias, kFastBias}, acc, bm + wm, bn + wn, lane);
-  else if constexpr (DIRECT) store_direct(g, acc, bm + wm, bn + wn, split, lane);
-  else store_tile(g, acc, smem, bm, bn, wm, wn, split, t, lane);
+  else store_direct(g, acc, bm + wm, bn + wn, split, lane);
 }
 
 // ---------------------------------------------------------------------------
@@ -340,17 +295,6 @@ constexpr int SK_BM = 64, SK_NT = 256;
 int g_sk_bn = std::getenv("CCMPI_SK_BN") ? std::atoi(std::getenv("CCMPI_SK_BN")) : 128;      // tuning knobs
 // grid cap; 0 = one balanced round (below)
 int g_sk_grid = std::getenv("CCMPI_SK_GRID") ? std::atoi(std::getenv("CCMPI_SK_GRID")) : 0;
-bool g_sk_nt = std::getenv("CCMPI_SK_NT") != nullptr;  // non-temporal bf16 stores (A/B knob)
-
-int device_cus() {
-  static int cus = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      return 256;
-    return n > 0 ? n : 256;
-  }();
-  return cus;
-}
 
 // Patch source for the fused embedding (PATCH = true): the A rows are generated
 // from the fp32 images instead of read -- token row m = (image m / S, patch m % S)
@@ -399,7 +343,7 @@ __host__ __device__ inline int sk_row_chunks(int K) {
 }
 inline size_t sk_lds_bytes(int skbn, int K) { return (size_t)(skbn + 2 * SK_BM) * sk_row_chunks(K) * 16; }
 
-template <int SK_BN, int FAST = 0, bool PATCH = false>  // FAST = 1 + out_bf16 (no accumulate / act, aligned C, N % 8 == 0), 0 = generic; 3 = bf16 non-temporal
+template <int SK_BN, int FAST = 0, bool PATCH = false>  // FAST = 1 + out_bf16 (no accumulate / act, aligned C, N % 8 == 0), 0 = generic
 __global__ void __launch_bounds__(SK_NT) k_gemm_smallk(GemmArgs g, int kp, PatchSrc ps) {
   constexpr int WN = SK_BN / 4;  // columns per wave
   constexpr int NP = WN / 32;    // column pairs (32 columns) per wave
@@ -503,17 +447,12 @@ __global__ void __launch_bounds__(SK_NT) k_gemm_smallk(GemmArgs g, int kp, Patch
 #pragma unroll
           for (int e = 0; e < 8; ++e) v[e] = g.alpha * acc[i][2 * pr + (e >> 2)][e & 3] + bias[pr][e];
           if (row < g.M && col < g.N) {
-            if constexpr (FAST >= 2) {
+            if constexpr (FAST == 2) {
               uint32_t w[4];
 #pragma unroll
               for (int q = 0; q < 4; ++q) w[q] = pk_bf16(v[2 * q], v[2 * q + 1]);
-              uint4* dst = reinterpret_cast<uint4*>(reinterpret_cast<uint16_t*>(g.C) + (size_t)row * g.ldc + col);
-              if constexpr (FAST == 3) {  // streaming (non-temporal) store: A/B knob for the write-bound case
-                typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
-                __builtin_nontemporal_store(u32x4v{w[0], w[1], w[2], w[3]}, reinterpret_cast<u32x4v*>(dst));
-              } else {
-                *dst = uint4{w[0], w[1], w[2], w[3]};
-              }
+              *reinterpret_cast<uint4*>(reinterpret_cast<uint16_t*>(g.C) + (size_t)row * g.ldc + col) =
+                  uint4{w[0], w[1], w[2], w[3]};
             } else {
               float4* C = reinterpret_cast<float4*>(reinterpret_cast<float*>(g.C) + (size_t)row * g.ldc + col);
               C[0] = make_float4(v[0], v[1], v[2], v[3]);
@@ -534,42 +473,7 @@ __global__ void __launch_bounds__(SK_NT) k_gemm_smallk(GemmArgs g, int kp, Patch
         float v[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = epi(g, acc[i][2 * pr + (e >> 2)][e & 3], bias[pr][e]);
-        if (vec_ok && col + 8 <= g.N) {
-          if (g.out_bf16) {
-            uint16_t* C = reinterpret_cast<uint16_t*>(g.C) + (size_t)row * g.ldc + col;
-            if (g.accumulate) {
-              const uint4 o = *reinterpret_cast<const uint4*>(C);
-              const uint32_t ow[4] = {o.x, o.y, o.z, o.w};
-#pragma unroll
-              for (int q = 0; q < 4; ++q) { v[2 * q] += bf16_lo(ow[q]); v[2 * q + 1] += bf16_hi(ow[q]); }
-            }
-            uint32_t w[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) w[q] = pk_bf16(v[2 * q], v[2 * q + 1]);
-            *reinterpret_cast<uint4*>(C) = uint4{w[0], w[1], w[2], w[3]};
-          } else {
-            float4* C = reinterpret_cast<float4*>(reinterpret_cast<float*>(g.C) + (size_t)row * g.ldc + col);
-            float4 o0 = make_float4(v[0], v[1], v[2], v[3]), o1 = make_float4(v[4], v[5], v[6], v[7]);
-            if (g.accumulate) {
-              const float4 p0 = C[0], p1 = C[1];
-              o0.x += p0.x; o0.y += p0.y; o0.z += p0.z; o0.w += p0.w;
-              o1.x += p1.x; o1.y += p1.y; o1.z += p1.z; o1.w += p1.w;
-            }
-            C[0] = o0;
-            C[1] = o1;
-          }
-        } else {
-          for (int e = 0; e < 8 && col + e < g.N; ++e) {
-            const size_t o = (size_t)row * g.ldc + col + e;
-            if (g.out_bf16) {
-              uint16_t* C = reinterpret_cast<uint16_t*>(g.C);
-              C[o] = (uint16_t)f32_to_bf16_bits(v[e] + (g.accumulate ? bf2f(C[o]) : 0.f));
-            } else {
-              float* C = reinterpret_cast<float*>(g.C);
-              C[o] = v[e] + (g.accumulate ? C[o] : 0.f);
-            }
-          }
-        }
+        store_row8(g, g.ldc, row, col, v, vec_ok && col + 8 <= g.N);  // per vector, as store_direct
       }
     }
     if (more) swrite(buf ^ 1);
@@ -720,7 +624,6 @@ void launch_smallk(const GemmArgs& g, int id, const PatchSrc& ps, hipStream_t st
                           reinterpret_cast<const void*>(k_gemm_smallk<128, 0>),
                           reinterpret_cast<const void*>(k_gemm_smallk<128, 1>),
                           reinterpret_cast<const void*>(k_gemm_smallk<128, 2>),
-                          reinterpret_cast<const void*>(k_gemm_smallk<128, 3>),
                           reinterpret_cast<const void*>(k_gemm_smallk<128, 2, true>)})
       ok = ok && hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
     return ok;
@@ -735,8 +638,7 @@ void launch_smallk(const GemmArgs& g, int id, const PatchSrc& ps, hipStream_t st
   } else if (id == 1) {
     hipLaunchKernelGGL((k_gemm_smallk<128, 1>), grid, dim3(SK_NT), lds, st, g, kp, ps);
   } else if (id == 2) {
-    if (g_sk_nt) hipLaunchKernelGGL((k_gemm_smallk<128, 3>), grid, dim3(SK_NT), lds, st, g, kp, ps);
-    else hipLaunchKernelGGL((k_gemm_smallk<128, 2>), grid, dim3(SK_NT), lds, st, g, kp, ps);
+    hipLaunchKernelGGL((k_gemm_smallk<128, 2>), grid, dim3(SK_NT), lds, st, g, kp, ps);
   } else {
     hipLaunchKernelGGL((k_gemm_smallk<128, 0>), grid, dim3(SK_NT), lds, st, g, kp, ps);
   }
@@ -796,12 +698,11 @@ void gemm_nt(uint64_t A, uint64_t B, uint64_t C, uint64_t bias, int M, int N, in
   if (g_kernel == 0 && splitk == 1 && g_ring_min_macs > 0 && (long long)M * N * K >= g_ring_min_macs &&
       M >= 1024 && N >= 1024 && ((g_ring_sched & 32768) || !(K > 16384 && gemm_w4_tiles(M, N) <= 256)) &&
       gemm_w4_ok(g) && gemm_w4r_fast(g)) {
-    launch_gemm_nt_w4r(g, reinterpret_cast<hipStream_t>(stream));
+    launch_gemm_ring(g, 0, 0, reinterpret_cast<hipStream_t>(stream));
     CCMPI_HIP_CHECK(hipGetLastError());
     return;
   }
-  const bool big_ok = K % (2 * BK) == 0 && g_use_glds;
-  if (big_ok && g_kernel != 1) {
+  if (K % (2 * BK) == 0 && g_kernel != 1) {
     int bn = 0;
     if (g_kernel == 2) bn = 256;
     else if (g_kernel == 3) bn = 128;
@@ -819,26 +720,22 @@ void gemm_nt(uint64_t A, uint64_t B, uint64_t C, uint64_t bias, int M, int N, in
       return;
     }
   }
-  if (K % BK == 0 && g_use_glds) {
-    if (g_direct_epi) {
-      const bool fast = splitk == 1 && !accumulate && act == 0 && N % 8 == 0 && ldc % 8 == 0 && (C % 16) == 0;
-      const int id = fast ? 1 + (out_bf16 ? 1 : 0) + 2 * bias_kind : 0;
-      auto st = reinterpret_cast<hipStream_t>(stream);
-      switch (id) {
-        case 1: hipLaunchKernelGGL((k_gemm_nt_glds<true, 1>), dim3(nwg), dim3(NT), 0, st, g); break;
-        case 2: hipLaunchKernelGGL((k_gemm_nt_glds<true, 2>), dim3(nwg), dim3(NT), 0, st, g); break;
-        case 3: hipLaunchKernelGGL((k_gemm_nt_glds<true, 3>), dim3(nwg), dim3(NT), 0, st, g); break;
-        case 4: hipLaunchKernelGGL((k_gemm_nt_glds<true, 4>), dim3(nwg), dim3(NT), 0, st, g); break;
-        case 5: hipLaunchKernelGGL((k_gemm_nt_glds<true, 5>), dim3(nwg), dim3(NT), 0, st, g); break;
-        case 6: hipLaunchKernelGGL((k_gemm_nt_glds<true, 6>), dim3(nwg), dim3(NT), 0, st, g); break;
-        default: hipLaunchKernelGGL((k_gemm_nt_glds<true, 0>), dim3(nwg), dim3(NT), 0, st, g); break;
-      }
+  auto st = reinterpret_cast<hipStream_t>(stream);
+  if (K % BK == 0) {
+    const bool fast = splitk == 1 && !accumulate && act == 0 && N % 8 == 0 && ldc % 8 == 0 && (C % 16) == 0;
+    const int id = fast ? 1 + (out_bf16 ? 1 : 0) + 2 * bias_kind : 0;
+    switch (id) {
+      case 1: hipLaunchKernelGGL(k_gemm_nt_glds<1>, dim3(nwg), dim3(NT), 0, st, g); break;
+      case 2: hipLaunchKernelGGL(k_gemm_nt_glds<2>, dim3(nwg), dim3(NT), 0, st, g); break;
+      case 3: hipLaunchKernelGGL(k_gemm_nt_glds<3>, dim3(nwg), dim3(NT), 0, st, g); break;
+      case 4: hipLaunchKernelGGL(k_gemm_nt_glds<4>, dim3(nwg), dim3(NT), 0, st, g); break;
+      case 5: hipLaunchKernelGGL(k_gemm_nt_glds<5>, dim3(nwg), dim3(NT), 0, st, g); break;
+      case 6: hipLaunchKernelGGL(k_gemm_nt_glds<6>, dim3(nwg), dim3(NT), 0, st, g); break;
+      default: hipLaunchKernelGGL(k_gemm_nt_glds<0>, dim3(nwg), dim3(NT), 0, st, g); break;
     }
-    else
-      hipLaunchKernelGGL(k_gemm_nt_glds<false>, dim3(nwg), dim3(NT), 0, reinterpret_cast<hipStream_t>(stream), g);
+  } else {
+    hipLaunchKernelGGL(k_gemm_nt, dim3(nwg), dim3(NT), 0, st, g);
   }
-  else
-    hipLaunchKernelGGL(k_gemm_nt, dim3(nwg), dim3(NT), 0, reinterpret_cast<hipStream_t>(stream), g);
   CCMPI_HIP_CHECK(hipGetLastError());
 }
 
@@ -976,35 +873,24 @@ void register_gemm_ops(pybind11::module_& m) {
         pybind11::arg("accumulate"), pybind11::arg("splitk"), pybind11::arg("stream"), pybind11::arg("workspace") = 0,
         pybind11::arg("variant") = 0, pybind11::arg("C2") = 0, pybind11::arg("ldc2") = 0, pybind11::arg("csplit") = 0,
         pybind11::call_guard<pybind11::gil_scoped_release>());
-  m.def("gemm_set_glds", [](bool on) { g_use_glds = on; }, "select LDS-DMA (True) or register staging");
   m.def("gemm_tn_set_prefetch", [](int pf) { g_tn_pf = pf; },
         "128x128 TN kernel: K tiles in flight (0 auto, 1, 2)", pybind11::arg("pf"));
-  m.def("gemm_set_direct_epilogue", [](bool on) { g_direct_epi = on; },
-        "128x128 LDS-DMA kernel: LDS-free epilogue (True) or LDS-staged rows");
   m.def("gemm_set_kernel", [](int k) { g_kernel = k; },
         "gemm_nt tile choice: 0 auto, 1 128x128, 2 256x256, 3 256x128, 4 256x192, 5 256x256 four-wave");
   m.def("gemm_set_w4_sched", [](int v) { g_w4_sched = v; },
         "four-wave kernel variant (benchmarks): bit 0 persistent grid, bit 1 MFMA-first group order");
-  m.def("gemm_set_w4_debug", [](uint64_t p) { g_w4_dbg = reinterpret_cast<unsigned long long*>(p); },
-        "four-wave ring STAMP diagnostic: device buffer of 4 uint64 per wave (benchmarks only)");
   m.def("gemm_set_ring_min", [](long long v) { g_ring_min_macs = v; },
         "gemm_nt auto: LDS-ring kernel from this many multiply-adds up (0 = never)");
   m.def("gemm_ring_launches", [] { return g_ring_launches; }, "LDS-ring GEMM launches so far (this process)");
-  m.def("gemm_set_pair_nobar", [](int v) { g_pair_nobar = v; }, "diagnostic: pair ring without its barrier (wrong results)");
   m.def("gemm_set_pair_ta", [](int v) { g_pair_ta = v; }, "K-major A alone on the pair-slot ring (1) or the 4-slot ring (0)");
   m.def("gemm_set_ring_sched", [](int v) { g_ring_sched = v; },
-        "auto-dispatched LDS-ring kernel variant: bit 3 ring, bit 14 pair slots (default), bit 0 persistent, bit 15 long K too; diagnostics: bits 5-6 / 13 ablations, bit 9 stamps");
+        "auto-dispatched LDS-ring kernel variant: bit 3 ring, bit 14 pair slots (default), bit 0 persistent, bit 15 long K too");
   m.def("gemm_set_w4_group_m", [](int v) { g_w4_group_m = v > 0 ? v : 8; }, "four-wave kernel group-M rows");
-  m.def("gemm_set_ablation", [](int e) {
-    g_pp_exp = e;
-    CCMPI_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_pp_exp_dev), &e, sizeof(int)));
-  }, "GEMM ablation bits (benchmarks only): 1/2/4 ping-pong kernel, 8 = skip the 128x128 epilogue");
   m.def("embed_patches", &embed_patches, "h = patches(x) . W^T (bf16), patch rows generated in-kernel and stored to xp",
         pybind11::arg("x"), pybind11::arg("W"), pybind11::arg("C"), pybind11::arg("B"), pybind11::arg("img"),
         pybind11::arg("p"), pybind11::arg("N"), pybind11::arg("K"), pybind11::arg("ldw"), pybind11::arg("ldc"),
         pybind11::arg("xp"), pybind11::arg("ld_xp"), pybind11::arg("stream"),
         pybind11::call_guard<pybind11::gil_scoped_release>());
-  m.def("gemm_set_smallk_nt", [](bool on) { g_sk_nt = on; }, "small-K kernel: non-temporal bf16 output stores");
   m.def("gemm_set_smallk", [](int bn, int grid) { g_sk_bn = bn; g_sk_grid = grid; },
         "small-K kernel: N slice (128 / 256, 0 = off) and grid cap (tuning)");
   m.def("transpose16", &transpose16, "dst[C,R] = src[R,C]^T for 16-bit elements",

@@ -100,17 +100,13 @@ __device__ __forceinline__ void wait_steady(int b_pieces) {
   else wait_vm<6>();
 }
 
-// EXP: ablation bits for benchmarks only (0 = production):
-//   1 = lax vmcnt (wait for nothing: WRONG results, isolates DMA-latency stalls)
-//   2 = no s_setprio around the MFMA cluster
-//   4 = no ping-pong stagger (both groups in lockstep)
 // TN: weight-gradient form C[N1][N2] = sum_m A[m][n1] B[m][n2] (g.M = N1, g.N = N2,
 // g.K = M).  Half-tiles are 64 reduction rows x 128 output indices, stored as
 // 256-B rows whose 32-B granules are XOR-swizzled by tn_swz(row); operands come
 // out of ds_read_b64_tr_b16 (conflict-free: 16 lanes read rows r..r+3 and, in the
 // other lane group, r+8..r+11 -> 8 distinct granules).  Split-K partials go to
 // workspace slices (g.C + split * N1 * N2) for k_splitk_reduce.
-template <int BN, int EXP = 0, int FAST = 0, bool TN = false>  // FAST: fast_epilogue_id (gemm_common.hpp)
+template <int BN, int FAST = 0, bool TN = false>  // FAST: fast_epilogue_id (gemm_common.hpp)
 __global__ void __launch_bounds__(PNT, 1) k_gemm_nt_pp(GemmArgs g) {
   using G = Geo<BN>;
   extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
@@ -248,7 +244,7 @@ __global__ void __launch_bounds__(PNT, 1) k_gemm_nt_pp(GemmArgs g) {
     bar();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (!(EXP & 2)) __builtin_amdgcn_s_setprio(1);
+    __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
@@ -256,17 +252,13 @@ __global__ void __launch_bounds__(PNT, 1) k_gemm_nt_pp(GemmArgs g) {
 #pragma unroll
         for (int j = 0; j < G::NJ; ++j)
           acc[mh][nh][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][ks], fb[j][ks], acc[mh][nh][i][j], 0, 0, 0);
-    if constexpr (!(EXP & 2)) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
     bar();
   };
   // retire the half-tile issued four phases ago (steady state) or everything (tail)
   auto retire = [&](bool tail) {
-    if constexpr (EXP & 1) {
-      if (tail) wait_vm<0>();
-    } else {
-      if (tail) wait_vm<0>();
-      else wait_steady(b_pieces);
-    }
+    if (tail) wait_vm<0>();
+    else wait_steady(b_pieces);
   };
 
   if (nk > 0) {
@@ -280,7 +272,7 @@ __global__ void __launch_bounds__(PNT, 1) k_gemm_nt_pp(GemmArgs g) {
     wait_steady(b_pieces);  // buf0 A0, B0 landed (the 4 younger stages may stay in flight)
   }
   __syncthreads();
-  if (!(EXP & 4) && grp == 1) bar();  // group 1 runs one barrier behind group 0
+  if (grp == 1) bar();  // group 1 runs one barrier behind group 0
 
   for (int kt = 0; kt < nk; kt += 2) {
     const bool tail = kt + 2 >= nk;  // no tiles beyond this pair: drain instead of counting
@@ -326,7 +318,7 @@ __global__ void __launch_bounds__(PNT, 1) k_gemm_nt_pp(GemmArgs g) {
     retire(tail);
     mma(1, 0, fb0);
   }
-  if (!(EXP & 4) && grp == 0) bar();  // re-align the groups
+  if (grp == 0) bar();  // re-align the groups
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
@@ -366,43 +358,41 @@ __global__ void __launch_bounds__(PNT, 1) k_gemm_nt_pp(GemmArgs g) {
 
 int gemm256_tiles(int M, int N, int bn) { return ((M + PM - 1) / PM) * ((N + bn - 1) / bn); }
 
-template <int BN, int EXP, int FAST = 0>
+template <int BN, int FAST>
 static void launch_pp(const GemmArgs& g, hipStream_t stream) {
   static bool attr = [] {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(k_gemm_nt_pp<BN, EXP, FAST>),
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(k_gemm_nt_pp<BN, FAST>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, Geo<BN>::Lds) == hipSuccess;
   }();
   (void)attr;
   const int nwg = gemm256_tiles(g.M, g.N, BN) * g.splitk;
-  hipLaunchKernelGGL((k_gemm_nt_pp<BN, EXP, FAST>), dim3(nwg), dim3(PNT), Geo<BN>::Lds, stream, g);
+  hipLaunchKernelGGL((k_gemm_nt_pp<BN, FAST>), dim3(nwg), dim3(PNT), Geo<BN>::Lds, stream, g);
 }
 
 // production launches: the common epilogues get branch-free instantiations
 template <int BN>
 static void launch_pp_prod(const GemmArgs& g, hipStream_t stream) {
   switch (fast_epilogue_id(g)) {
-    case 1: return launch_pp<BN, 0, 1>(g, stream);  // fp32 out, no bias
-    case 2: return launch_pp<BN, 0, 2>(g, stream);  // bf16 out, no bias
-    case 4: return launch_pp<BN, 0, 4>(g, stream);  // bf16 out, fp32 bias
-    default: return launch_pp<BN, 0, 0>(g, stream);
+    case 1: return launch_pp<BN, 1>(g, stream);  // fp32 out, no bias
+    case 2: return launch_pp<BN, 2>(g, stream);  // bf16 out, no bias
+    case 4: return launch_pp<BN, 4>(g, stream);  // bf16 out, fp32 bias
+    default: return launch_pp<BN, 0>(g, stream);
   }
 }
-
-int g_pp_exp = 0;  // ablation variant (benchmarks only)
 
 void launch_gemm_tn_256(const GemmArgs& g, hipStream_t stream) {
   // partial tiles (split-K) or a plain fp32 tile: branch-free epilogue; accumulate -> generic
   if (g.splitk > 1 || !g.accumulate) {
-    static bool attr = hipFuncSetAttribute(reinterpret_cast<const void*>(k_gemm_nt_pp<256, 0, 1, true>),
+    static bool attr = hipFuncSetAttribute(reinterpret_cast<const void*>(k_gemm_nt_pp<256, 1, true>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, Geo<256>::Lds) == hipSuccess;
     (void)attr;
-    hipLaunchKernelGGL((k_gemm_nt_pp<256, 0, 1, true>), dim3(gemm256_tiles(g.M, g.N, 256) * g.splitk), dim3(PNT),
+    hipLaunchKernelGGL((k_gemm_nt_pp<256, 1, true>), dim3(gemm256_tiles(g.M, g.N, 256) * g.splitk), dim3(PNT),
                        Geo<256>::Lds, stream, g);
   } else {
-    static bool attr = hipFuncSetAttribute(reinterpret_cast<const void*>(k_gemm_nt_pp<256, 0, 0, true>),
+    static bool attr = hipFuncSetAttribute(reinterpret_cast<const void*>(k_gemm_nt_pp<256, 0, true>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, Geo<256>::Lds) == hipSuccess;
     (void)attr;
-    hipLaunchKernelGGL((k_gemm_nt_pp<256, 0, 0, true>), dim3(gemm256_tiles(g.M, g.N, 256) * g.splitk), dim3(PNT),
+    hipLaunchKernelGGL((k_gemm_nt_pp<256, 0, true>), dim3(gemm256_tiles(g.M, g.N, 256) * g.splitk), dim3(PNT),
                        Geo<256>::Lds, stream, g);
   }
 }
@@ -410,13 +400,7 @@ void launch_gemm_tn_256(const GemmArgs& g, hipStream_t stream) {
 void launch_gemm_nt_256(const GemmArgs& g, int bn, hipStream_t stream) {
   if (bn == 128) return launch_pp_prod<128>(g, stream);
   if (bn == 192) return launch_pp_prod<192>(g, stream);
-  switch (g_pp_exp) {
-    case 1: return launch_pp<256, 1>(g, stream);
-    case 2: return launch_pp<256, 2>(g, stream);
-    case 4: return launch_pp<256, 4>(g, stream);
-    case 6: return launch_pp<256, 6>(g, stream);
-    default: return launch_pp_prod<256>(g, stream);
-  }
+  return launch_pp_prod<256>(g, stream);
 }
 
 }  // namespace gemm

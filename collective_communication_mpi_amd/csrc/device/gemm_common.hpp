@@ -150,6 +150,50 @@ __device__ __forceinline__ void store_rows_fast(const GemmArgs& g, const float* 
   }
 }
 
+// The generic epilogues' row store: 8 consecutive columns of one row (v already
+// alpha/bias/act-applied) to C at (row, col), row < M and col < N.  `vec`: as 16-B vectors
+// (one bf16, two fp32; the caller has checked alignment and col + 8 <= N); otherwise per
+// element up to column N.  Both forms honour out_bf16 and accumulate.
+__device__ __forceinline__ void store_row8(const GemmArgs& g, int ldc, int row, int col, float (&v)[8], bool vec) {
+  if (vec) {
+    if (g.out_bf16) {
+      uint16_t* C = reinterpret_cast<uint16_t*>(g.C) + (size_t)row * ldc + col;
+      if (g.accumulate) {
+        const uint4 o = *reinterpret_cast<const uint4*>(C);
+        const uint32_t ow[4] = {o.x, o.y, o.z, o.w};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { v[2 * q] += bf16_lo(ow[q]); v[2 * q + 1] += bf16_hi(ow[q]); }
+      }
+      uint32_t w[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) w[q] = pk_bf16(v[2 * q], v[2 * q + 1]);
+      *reinterpret_cast<uint4*>(C) = uint4{w[0], w[1], w[2], w[3]};
+    } else {
+      float4* C = reinterpret_cast<float4*>(reinterpret_cast<float*>(g.C) + (size_t)row * ldc + col);
+      float4 o0 = make_float4(v[0], v[1], v[2], v[3]), o1 = make_float4(v[4], v[5], v[6], v[7]);
+      if (g.accumulate) {
+        const float4 p0 = C[0], p1 = C[1];
+        o0.x += p0.x; o0.y += p0.y; o0.z += p0.z; o0.w += p0.w;
+        o1.x += p1.x; o1.y += p1.y; o1.z += p1.z; o1.w += p1.w;
+      }
+      C[0] = o0;
+      C[1] = o1;
+    }
+  } else {
+#pragma unroll 1  // a loop, as the compiler kept it in the kernels: unrolled, the four-wave kernels grow by a fifth
+    for (int e = 0; e < 8 && col + e < g.N; ++e) {
+      const size_t o = (size_t)row * ldc + col + e;
+      if (g.out_bf16) {
+        uint16_t* C = reinterpret_cast<uint16_t*>(g.C);
+        C[o] = (uint16_t)f32_to_bf16_bits(v[e] + (g.accumulate ? bf2f(C[o]) : 0.f));
+      } else {
+        float* C = reinterpret_cast<float*>(g.C);
+        C[o] = v[e] + (g.accumulate ? C[o] : 0.f);
+      }
+    }
+  }
+}
+
 // Fast-epilogue id shared by the kernels: 1 + out_bf16 + 2 * bias_kind when the
 // epilogue needs no split-K, accumulate, activation or unaligned stores; 0 otherwise.
 inline int fast_epilogue_id(const GemmArgs& g) {
@@ -157,6 +201,17 @@ inline int fast_epilogue_id(const GemmArgs& g) {
   const bool ok = g.splitk == 1 && !g.accumulate && g.act == 0 && g.N % 8 == 0 &&
                   (((uint64_t)g.C | ((uint64_t)g.ldc * es)) % 16) == 0;
   return ok ? 1 + (g.out_bf16 ? 1 : 0) + 2 * g.bias_kind : 0;
+}
+
+// Compute units of the current device (256 when the query fails), asked once per process.
+inline int device_cus() {
+  static const int cus = [] {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+      return 256;
+    return n > 0 ? n : 256;
+  }();
+  return cus;
 }
 
 // XCD-aware bijective workgroup remap: blocks b, b+8, b+16, ... (dispatched
@@ -203,28 +258,25 @@ int gemm_w4_tiles(int M, int N);
 // 256 x bn (bn = 256 or 128) 8-wave ping-pong kernel (gemm256.hip); requires K % 128 == 0.
 void launch_gemm_nt_256(const GemmArgs& g, int bn, hipStream_t stream);
 int gemm256_tiles(int M, int N, int bn);
-extern int g_pp_exp;
 // TN (weight-gradient) form of the 256x256 ping-pong kernel; K (reduction rows) % 128 == 0,
 // N1, N2 % 8 == 0.  splitk > 1: g.C is a workspace of splitk fp32 [N1][N2] slices.
 void launch_gemm_tn_256(const GemmArgs& g, hipStream_t stream);
 // 256 x 256 four-wave kernel (gemm_w4.hip): 128 x 128 per wave, K % 64 == 0, no split-K
 bool gemm_w4_ok(const GemmArgs& g);
-extern int g_pair_nobar;  // diagnostic: pair ring without its odd-phase barrier (wrong results)
 extern int g_pair_ta;     // K-major A alone on the pair-slot ring (CCMPI_PAIR_TA; gemm_set_pair_ta)
 extern int g_ring_sched;  // auto-dispatched LDS-ring kernel variant (gemm_w4.hip launch_gemm_ring)
 extern long long g_ring_launches;  // launch_gemm_ring calls (tests: the ring path really ran)
 extern int g_w4_sched;    // four-wave kernel variant: bit 0 persistent grid, bit 1 MFMA-first group order
-extern unsigned long long* g_w4_dbg;  // four-wave ring STAMP diagnostic output (benchmarks)
 extern int g_w4_group_m;  // four-wave kernel: tile rows per group-M block
 void launch_gemm_nt_w4(const GemmArgs& g, hipStream_t stream);
 bool gemm_w4r_fast(const GemmArgs& g);  // the LDS-ring kernel's fast epilogue applies
-void launch_gemm_nt_w4r(const GemmArgs& g, hipStream_t stream);  // LDS-ring kernel (sched bits from g_w4_sched)
-// LDS-ring kernel with operand layouts: ta / tb = 1 reads A / B K-major ([K][M] / [K][N])
+// LDS-ring kernel with operand layouts: ta / tb = 1 reads A / B K-major ([K][M] / [K][N]);
+// its schedule comes from g_w4_sched when that has bit 3 set, else from g_ring_sched
 bool gemm_ring_ok(const GemmArgs& g, int ta, int tb);
 // push / push_rows: EPI 1 stores output row block j (push_rows rows) at push[j] instead of C
 void launch_gemm_ring(const GemmArgs& g, int ta, int tb, hipStream_t stream, uint16_t* glu = nullptr, int ldglu = 0,
                       uint16_t* const* push = nullptr, int push_rows = 0);
-extern long long g_ring_min_macs;  // gemm_nt auto: the LDS-ring kernel from this many MACs up (0 = never)  // ablation variant of the ping-pong kernel (benchmarks only; 0 = production)
+extern long long g_ring_min_macs;  // gemm_nt auto: the LDS-ring kernel from this many MACs up (0 = never)
 
 }  // namespace gemm
 }  // namespace dev

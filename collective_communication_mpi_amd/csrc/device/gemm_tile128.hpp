@@ -127,8 +127,8 @@ __device__ __forceinline__ void nt_mfmas(const bf16x8 (&af)[2][4], const bf16x8 
 // the (row & 7) chunk swizzle the fragment reads expect is applied to the per-lane
 // SOURCE address (the same involution on both sides).  Rows past a_end / b_end
 // re-read the last valid row (their outputs are discarded, and nothing outside the
-// valid rows is touched); only for K % 64 == 0.  `wave` must be wave-uniform.
-template <bool DIRECT>
+// valid rows is touched); only for K % 64 == 0.  `wave` must be wave-uniform.  Always the
+// DIRECT form (swapped MFMA operands, pair-permuted B rows; nt_mfmas).
 __device__ __forceinline__ void nt_loop_glds(const NtSrc& s, unsigned char* smem, floatx4 (&acc)[4][4], int wave,
                                              int lane) {
   const NtFragOff fo = nt_frag_off((wave >> 1) * 64, (wave & 1) * 64, lane);
@@ -140,7 +140,7 @@ __device__ __forceinline__ void nt_loop_glds(const NtSrc& s, unsigned char* smem
       const int q = wave * 4 + i;                 // 1 KiB LDS chunk = rows q*8 .. q*8+7
       const int r = q * 8 + lrow;
       const int c = pchunk ^ (r & 7);             // logical k-chunk this lane must fetch
-      const int ga = min(s.bm + r, s.a_end - 1), gb = min(s.bn + (DIRECT ? pair_perm(r) : r), s.b_end - 1);
+      const int ga = min(s.bm + r, s.a_end - 1), gb = min(s.bn + pair_perm(r), s.b_end - 1);
       __builtin_amdgcn_global_load_lds((const void*)(s.A + (size_t)ga * s.lda + k0 + c * 8),
                                        (__attribute__((address_space(3))) void*)(nt_as(smem, buf) + q * 1024), 16, 0, 0);
       __builtin_amdgcn_global_load_lds((const void*)(s.B + (size_t)gb * s.ldb + k0 + c * 8),
@@ -169,7 +169,7 @@ __device__ __forceinline__ void nt_loop_glds(const NtSrc& s, unsigned char* smem
     nt_read_frags(nt_as(smem, cur), fo, af, bf);
     if (kt + 1 < s.nk) issue((s.kt0 + kt + 1) * BK, cur ^ 1);
     __builtin_amdgcn_s_setprio(1);
-    nt_mfmas<DIRECT>(af, bf, acc);
+    nt_mfmas<true>(af, bf, acc);
     __builtin_amdgcn_s_setprio(0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();

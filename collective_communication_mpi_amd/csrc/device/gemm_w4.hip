@@ -52,17 +52,12 @@ struct W4Args {
   GemmArgs g;
   int group_m;  // tile rows per group of the group-M order
   FusedArgs f;  // FUSED only
-  unsigned long long* dbg;  // STAMP diagnostic builds only: 4 cycle counts per wave
   uint16_t* glu;  // EPI 2 only: silu(gate) * up of each interleaved (gate, up) column pair
   int ldglu;
   // EPI 1 push mode (push_rows > 0): output row block j = rows [j * push_rows, (j + 1) *
   // push_rows) goes to push[j] (row 0 of the block at push[j]; a peer's inbox slot), not C
   int push_rows;
   uint16_t* push[kMaxRanks];
-  // diagnostic (gemm_set_pair_nobar, wrong results): the pair ring's odd-phase sync reduced to
-  // the wave's own waits (1), to the barrier without the DMA wait (2), or to neither (3) --
-  // upper bounds of removing the barrier's skew / the DMA latency stalls
-  int nobar;
 };
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t op_rsrc(const uint16_t* base, long rows, int ld) {
@@ -361,9 +356,10 @@ __global__ void __launch_bounds__(WNT, 1) k_gemm_w4(W4Args wa) {
   };
 
   const int es = g.out_bf16 ? 2 : 4;
+  // per tile: with N % 8 != 0 every row vector goes element by element (gemm.hip decides per vector)
   const bool vec_ok = (((uint64_t)g.C | ((uint64_t)g.ldc * es)) % 16) == 0 && g.N % 8 == 0;
   const int step = PERSIST ? (int)gridDim.x : ntiles;
-  int lt = PERSIST ? slot : slot;  // logical tile
+  int lt = slot;  // logical tile
   if (lt >= ntiles) return;
   int tm, tn;
   tile_coords(lt, tiles_m, tiles_n, wa.group_m, tm, tn);
@@ -448,15 +444,7 @@ __global__ void __launch_bounds__(WNT, 1) k_gemm_w4(W4Args wa) {
 #pragma unroll
     for (int h = 0; h < 4; ++h) {
       __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            tile[(i * 16 + (lane >> 4) * 4 + r) * kEpiTS + j * 16 + (lane & 15)] = acc[h * 2 + i][j][r];
-      // the slab is this wave's own and a wave's LDS accesses run in order: no barrier
-      __builtin_amdgcn_wave_barrier();
+      to_slab(h);
 #pragma unroll 1
       for (int it = 0; it < 8; ++it) {
         const int rl = it * 4 + (lane >> 4);
@@ -468,42 +456,7 @@ __global__ void __launch_bounds__(WNT, 1) k_gemm_w4(W4Args wa) {
         v[0] = x0.x; v[1] = x0.y; v[2] = x0.z; v[3] = x0.w; v[4] = x1.x; v[5] = x1.y; v[6] = x1.z; v[7] = x1.w;
 #pragma unroll
         for (int q = 0; q < 8; ++q) v[q] = epi(g, v[q], bias[q]);
-        if (vec_ok) {
-          if (g.out_bf16) {
-            uint16_t* C = reinterpret_cast<uint16_t*>(g.C) + (size_t)row * g.ldc + col;
-            if (g.accumulate) {
-              const uint4 o = *reinterpret_cast<const uint4*>(C);
-              const uint32_t ow[4] = {o.x, o.y, o.z, o.w};
-#pragma unroll
-              for (int q = 0; q < 4; ++q) { v[2 * q] += bf16_lo(ow[q]); v[2 * q + 1] += bf16_hi(ow[q]); }
-            }
-            uint32_t w[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) w[q] = pk_bf16(v[2 * q], v[2 * q + 1]);
-            *reinterpret_cast<uint4*>(C) = uint4{w[0], w[1], w[2], w[3]};
-          } else {
-            float* C = reinterpret_cast<float*>(g.C) + (size_t)row * g.ldc + col;
-            float4 y0 = make_float4(v[0], v[1], v[2], v[3]), y1 = make_float4(v[4], v[5], v[6], v[7]);
-            if (g.accumulate) {
-              const float4 o0 = *reinterpret_cast<const float4*>(C), o1 = *reinterpret_cast<const float4*>(C + 4);
-              y0.x += o0.x; y0.y += o0.y; y0.z += o0.z; y0.w += o0.w;
-              y1.x += o1.x; y1.y += o1.y; y1.z += o1.z; y1.w += o1.w;
-            }
-            *reinterpret_cast<float4*>(C) = y0;
-            *reinterpret_cast<float4*>(C + 4) = y1;
-          }
-        } else {
-          for (int q = 0; q < 8 && col + q < g.N; ++q) {
-            const size_t o = (size_t)row * g.ldc + col + q;
-            if (g.out_bf16) {
-              uint16_t* C = reinterpret_cast<uint16_t*>(g.C);
-              C[o] = (uint16_t)f32_to_bf16_bits(v[q] + (g.accumulate ? bf2f(C[o]) : 0.f));
-            } else {
-              float* C = reinterpret_cast<float*>(g.C);
-              C[o] = v[q] + (g.accumulate ? C[o] : 0.f);
-            }
-          }
-        }
+        store_row8(g, g.ldc, row, col, v, vec_ok);
       }
       __builtin_amdgcn_wave_barrier();
     }
@@ -596,10 +549,6 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t op_rsrc_t(const uint16_t* X, i
 // EPI 2: EPI 1 plus the SwiGLU gate of interleaved (gate, up) output column pairs:
 // glu[r, c / 2] = silu(C[r, c]) * C[r, c + 1] for even c, from the bf16-rounded C (the
 // values the unfused gate would read), one 8-B store next to each 16-B row store.
-// ABL (diagnostic ablations, wrong results): bit 2 reads whole 128-B lines per DMA piece
-// (8 rows instead of 16 half lines); bit 0 drops the steady-state DMA, bit 1 the
-// steady-state fragment reads.  STAMP (diagnostic): per wave, s_memtime cycles of the
-// prologue, main loop, epilogue and the phase-end waits -> wa.dbg (first tile only).
 // TA / TB: operand layout.  0 ("N"): rows of K contiguous elements (A[m][k], B[n][k]).
 // 1 ("T", K-major): stored [K][M] / [K][N] (dX = dY W reads W this way, dW = dY^T X both
 // operands).  A K-major slot half is [32 k][256 rows] with 512-B k-rows whose 32-B
@@ -608,24 +557,21 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t op_rsrc_t(const uint16_t* X, i
 // (Phase placements tried and measured no faster -- reads first / DMA last, odd waves one
 // MFMA later, one M0 chain per phase, and for the pair ring front-loaded DMA -- were
 // removed; their A/B records: profiles/r4_gemm, profiles/r4_pair2.)
-// PAIR (N-layout A; B N-layout or K-major; no diagnostics): the pair-slot ring.  Each DMA piece
-// reads 8 whole 128-B lines (8 rows x 64 k) instead of 16 half lines: the 16 x 64-B
-// pieces of the 4-slot ring cost 13-16 % against hipBLASLt (profiles/r4_gemm, ABL bit 2
-// ablation).  Two slots of one K pair each (kPair): phase q computes step q-1 and reads
-// step q from slot (q >> 1) & 1; even phase 2p issues the 16 pieces of pair p+1 into the
-// other slot, whose last reader was phase 2p-1; only odd phases end in a barrier (pair
-// p+1 landed everywhere, slot p free).
-template <int EPI, int PERSIST, int ABL = 0, int STAMP = 0, int TA = 0, int TB = 0, int PAIR = 0>
+// PAIR: the pair-slot ring.  Each DMA piece reads 8 whole 128-B lines (8 rows x 64 k)
+// instead of 16 half lines: the 16 x 64-B pieces of the 4-slot ring cost 13-16 % against
+// hipBLASLt (profiles/r4_gemm; measured with a whole-line ablation build, since removed).
+// Two slots of one K pair each (kPair): phase q computes step q-1 and reads step q from
+// slot (q >> 1) & 1; even phase 2p issues the 16 pieces of pair p+1 into the other slot,
+// whose last reader was phase 2p-1; only odd phases end in a barrier (pair p+1 landed
+// everywhere, slot p free).
+template <int EPI, int PERSIST, int TA, int TB, int PAIR>
 __global__ void __launch_bounds__(WNT, 1) k_gemm_w4r(W4Args wa) {
-  static_assert(!PAIR || (!ABL && !STAMP), "pair-slot ring: no diagnostics");
   const GemmArgs& g = wa.g;
   extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
   const int tiles_n = (g.N + WNB - 1) / WNB, tiles_m = (g.M + WM - 1) / WM;
   const int ntiles = tiles_n * tiles_m;
   int lt = xcd_remap(blockIdx.x, gridDim.x);
   if (lt >= ntiles) return;
-  const unsigned long long t_start = STAMP ? __builtin_amdgcn_s_memtime() : 0;
-  unsigned long long t_wait = 0, t_loop = 0, t_epi = 0;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wr = wave >> 1, wc = wave & 1;
@@ -644,10 +590,8 @@ __global__ void __launch_bounds__(WNT, 1) k_gemm_w4r(W4Args wa) {
 
   // DMA piece i of a step: 16 rows x 64 B; wave w covers rows (4 i + w) * 16 ..
   // lane l: row + (l >> 2), physical chunk l & 3 <- logical chunk (l & 3) ^ f((l >> 4) & 3)
-  // (ABL bit 2, diagnostic: each piece reads 8 rows x 128 B -- whole cache lines, as
-  // hipBLASLt's 64-deep K tiles do -- instead of 16 rows x 64 B; wrong results)
-  const int drow = (ABL & 4) ? wave * 16 + (lane >> 3) : wave * 16 + (lane >> 2);
-  const int dchunk = (ABL & 4) ? (lane & 7) << 4 : ((lane & 3) ^ ring_swz((lane >> 4) & 3)) << 4;
+  const int drow = wave * 16 + (lane >> 2);
+  const int dchunk = ((lane & 3) ^ ring_swz((lane >> 4) & 3)) << 4;
   const int va = drow * g.lda * 2 + dchunk, vb = drow * g.ldb * 2 + dchunk;
   // K-major pieces: 2 k-rows x 512 B; wave w, piece i: k-rows 8 i + 2 w + (l >> 5); lane l
   // lands at granule (l & 31) >> 1, half l & 1, holding logical granule ^ tn_swz(k-row)
@@ -664,8 +608,7 @@ __global__ void __launch_bounds__(WNT, 1) k_gemm_w4r(W4Args wa) {
   const int sa2 = 2 * sa1, sa3 = 3 * sa1, sb2 = 2 * sb1, sb3 = 3 * sb1;
   const int ka = TA ? 64 * g.lda : 64, kb = TB ? 64 * g.ldb : 64;  // bytes per K-step
   auto dma_step = [&](int s) {
-    const int sk = (ABL & 4) ? (s >> 1) * 2 : s;  // ABL 4: 128-B aligned K windows
-    return DmaStep{smem + (s & 3) * kRing + wave * 1024, ta0 + sk * ka, tb0 + sk * kb, ta1 + sk * ka, tb1 + sk * kb};
+    return DmaStep{smem + (s & 3) * kRing + wave * 1024, ta0 + s * ka, tb0 + s * kb, ta1 + s * ka, tb1 + s * kb};
   };
   auto dma_piece = [&](const DmaStep& d, int i) {
     const bool isa = i < 4;
@@ -814,34 +757,28 @@ __global__ void __launch_bounds__(WNT, 1) k_gemm_w4r(W4Args wa) {
         // K-major operands need ~16 more VGPRs of read offsets: A fragments are
         // replaced in place (pa == ca), block i read right after its last MFMA
         mm(0, 1);
-        if constexpr (!(ABL & 2)) rd1(q, i >> 1, i & 1, ca, cb);  // B block i
+        rd1(q, i >> 1, i & 1, ca, cb);  // B block i
         __builtin_amdgcn_sched_barrier(0);
         mm(1, 3);
-        if constexpr (DMA && !(ABL & 1)) dma_piece(ds, i);
+        if constexpr (DMA) dma_piece(ds, i);
         __builtin_amdgcn_sched_barrier(0);
         mm(3, 8);
-        if constexpr (!(ABL & 2)) rd1(q, 4 + (i >> 1), i & 1, ca, cb);  // A block i
+        rd1(q, 4 + (i >> 1), i & 1, ca, cb);  // A block i
         __builtin_amdgcn_sched_barrier(0);
       } else {
         mm(0, 1);
-        if constexpr (!(ABL & 2)) rd1(q, i, 0, ca, cb);
+        rd1(q, i, 0, ca, cb);
         __builtin_amdgcn_sched_barrier(0);
         mm(1, 3);
-        if constexpr (DMA && !(ABL & 1)) dma_piece(ds, i);
+        if constexpr (DMA) dma_piece(ds, i);
         __builtin_amdgcn_sched_barrier(0);
         mm(3, 5);
-        if constexpr (!(ABL & 2)) rd1(q, i, 1, ca, cb);
+        rd1(q, i, 1, ca, cb);
         __builtin_amdgcn_sched_barrier(0);
         mm(5, 8);
       }
     }
-    if constexpr (STAMP) {
-      const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-      ring_wait_barrier_c<YOUNGER>();
-      t_wait += __builtin_amdgcn_s_memtime() - t0;
-    } else {
-      ring_wait_barrier_c<YOUNGER>();
-    }
+    ring_wait_barrier_c<YOUNGER>();
   };
   using T = std::true_type;
   using F = std::false_type;
@@ -877,23 +814,7 @@ __global__ void __launch_bounds__(WNT, 1) k_gemm_w4r(W4Args wa) {
       __builtin_amdgcn_sched_barrier(0);
       mm(5, 8);
     }
-    if constexpr (ODD) {
-      if (wa.nobar == 1) {  // own waits only, no barrier
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-      } else if (wa.nobar == 2) {  // barrier, DMA not waited for
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-      } else if (wa.nobar == 3) {  // neither
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-      } else {
-        ring_wait_barrier_c<0>();
-      }
-    }
+    if constexpr (ODD) ring_wait_barrier_c<0>();
   };
 
   const int ldc = g.ldc;
@@ -966,7 +887,6 @@ __global__ void __launch_bounds__(WNT, 1) k_gemm_w4r(W4Args wa) {
       if (nst >= 4) dma(3, i);
     }
     ring_wait_barrier(nst >= 4 ? 16 : 0);
-    if (STAMP) t_loop = __builtin_amdgcn_s_memtime();
     // steady state: phases 1 .. nst-4 in pairs, each prefetching the step three ahead
     // (K-major variants: one A set, a1 aliases a0)
     bf16x8 (&a1r)[8] = (TA || TB) ? a0 : a1;
@@ -995,7 +915,6 @@ __global__ void __launch_bounds__(WNT, 1) k_gemm_w4r(W4Args wa) {
 #pragma unroll
       for (int j = 0; j < 8; ++j) mfma(i, j, a1r[i], b1[j]);
     }
-    if (STAMP) t_epi = __builtin_amdgcn_s_memtime();
 
     if constexpr (EPI == 1 || EPI == 2) {
       // ---- fast epilogue: per 32-row pass, bf16 pairs -> slab (slot 3, 8 KiB per wave,
@@ -1068,7 +987,7 @@ __global__ void __launch_bounds__(WNT, 1) k_gemm_w4r(W4Args wa) {
 #pragma unroll
       for (int q = 0; q < 8; ++q) bias[q] = load_bias(g, col + q, 0);
       const int es = g.out_bf16 ? 2 : 4;
-      const bool vec_ok = (((uint64_t)g.C | ((uint64_t)ldc * es)) % 16) == 0 && g.N % 8 == 0;
+      const bool vec_ok = (((uint64_t)g.C | ((uint64_t)ldc * es)) % 16) == 0 && g.N % 8 == 0;  // per tile, as k_gemm_w4
 #pragma unroll
       for (int h = 0; h < 4; ++h) {
         __builtin_amdgcn_sched_barrier(0);
@@ -1091,42 +1010,7 @@ __global__ void __launch_bounds__(WNT, 1) k_gemm_w4r(W4Args wa) {
           v[0] = x0.x; v[1] = x0.y; v[2] = x0.z; v[3] = x0.w; v[4] = x1.x; v[5] = x1.y; v[6] = x1.z; v[7] = x1.w;
 #pragma unroll
           for (int q = 0; q < 8; ++q) v[q] = epi(g, v[q], bias[q]);
-          if (vec_ok) {
-            if (g.out_bf16) {
-              uint16_t* C = reinterpret_cast<uint16_t*>(g.C) + (size_t)row * ldc + col;
-              if (g.accumulate) {
-                const uint4 o = *reinterpret_cast<const uint4*>(C);
-                const uint32_t ow[4] = {o.x, o.y, o.z, o.w};
-#pragma unroll
-                for (int q = 0; q < 4; ++q) { v[2 * q] += bf16_lo(ow[q]); v[2 * q + 1] += bf16_hi(ow[q]); }
-              }
-              uint32_t w[4];
-#pragma unroll
-              for (int q = 0; q < 4; ++q) w[q] = pk_bf16(v[2 * q], v[2 * q + 1]);
-              *reinterpret_cast<uint4*>(C) = uint4{w[0], w[1], w[2], w[3]};
-            } else {
-              float* C = reinterpret_cast<float*>(g.C) + (size_t)row * ldc + col;
-              float4 y0 = make_float4(v[0], v[1], v[2], v[3]), y1 = make_float4(v[4], v[5], v[6], v[7]);
-              if (g.accumulate) {
-                const float4 o0 = *reinterpret_cast<const float4*>(C), o1 = *reinterpret_cast<const float4*>(C + 4);
-                y0.x += o0.x; y0.y += o0.y; y0.z += o0.z; y0.w += o0.w;
-                y1.x += o1.x; y1.y += o1.y; y1.z += o1.z; y1.w += o1.w;
-              }
-              *reinterpret_cast<float4*>(C) = y0;
-              *reinterpret_cast<float4*>(C + 4) = y1;
-            }
-          } else {
-            for (int q = 0; q < 8 && col + q < g.N; ++q) {
-              const size_t o = (size_t)row * ldc + col + q;
-              if (g.out_bf16) {
-                uint16_t* C = reinterpret_cast<uint16_t*>(g.C);
-                C[o] = (uint16_t)f32_to_bf16_bits(v[q] + (g.accumulate ? bf2f(C[o]) : 0.f));
-              } else {
-                float* C = reinterpret_cast<float*>(g.C);
-                C[o] = v[q] + (g.accumulate ? C[o] : 0.f);
-              }
-            }
-          }
+          store_row8(g, ldc, row, col, v, vec_ok);
         }
         __builtin_amdgcn_wave_barrier();
       }
@@ -1140,19 +1024,6 @@ __global__ void __launch_bounds__(WNT, 1) k_gemm_w4r(W4Args wa) {
       const bool interior = bm + WM <= g.M && bn + WNB <= g.N;
       younger = !interior ? younger0 : (EPI == 2 ? 63 : younger0 + 32);
     }
-    if constexpr (STAMP) {
-      if (lt == xcd_remap(blockIdx.x, gridDim.x)) {  // first tile of this workgroup
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned long long t_end = __builtin_amdgcn_s_memtime();
-        if (lane == 0) {
-          unsigned long long* d = wa.dbg + ((size_t)blockIdx.x * 4 + wave) * 4;
-          d[0] = t_loop - t_start;
-          d[1] = t_epi - t_loop;
-          d[2] = t_end - t_epi;
-          d[3] = t_wait;
-        }
-      }
-    }
     if (!more) break;
     lt = next;
     tm = ntm;
@@ -1164,15 +1035,13 @@ __global__ void __launch_bounds__(WNT, 1) k_gemm_w4r(W4Args wa) {
 }  // namespace
 
 int g_w4_sched = 1;   // bit 0: persistent grid, bit 1: MFMA-first order inside groups, bit 2: front-loaded DMA,
-                      // bit 3: LDS-ring kernel (k_gemm_w4r), bits 5-6 / 9: its ablations / stamps
+                      // bit 3: LDS-ring kernel (k_gemm_w4r)
 int g_w4_group_m = 8;
-unsigned long long* g_w4_dbg = nullptr;
 long long g_ring_launches = 0;
 // auto dispatch: the pair-slot ring (0.93-0.95x hipBLASLt on the Llama MLP shapes against
 // 0.86-0.89x for the 4-slot ring, profiles/r4_pair); CCMPI_RING_SCHED overrides (A/B runs)
 // K-major A on the pair ring without K-major B (CCMPI_PAIR_TA=1): the TA + TB form is the
 // default for dW = dY^T X; A alone goes to the 4-slot ring unless asked for
-int g_pair_nobar = 0;
 int g_pair_ta = std::getenv("CCMPI_PAIR_TA") ? std::atoi(std::getenv("CCMPI_PAIR_TA")) : 0;
 int g_ring_sched = std::getenv("CCMPI_RING_SCHED") ? std::atoi(std::getenv("CCMPI_RING_SCHED")) : (8 | 16384);
 long long g_ring_min_macs = std::getenv("CCMPI_RING_MIN_MACS") ? std::atoll(std::getenv("CCMPI_RING_MIN_MACS")) : (1ll << 33);
@@ -1197,22 +1066,40 @@ __global__ void __launch_bounds__(256) k_fused_wait(FusedArgs f, int tiles) {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
 }
 
-static void w4_attr(const void* f) {
-  (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kLds4 + kLdsExtra);
+// One launcher per instantiation: it raises that instantiation's dynamic-LDS limit on first
+// use (not a stream operation, so legal under graph capture), then launches.
+template <int PERSIST, int ORDER, int FUSED = 0, int FRONT = 0>
+static void launch_w4(int grid, const W4Args& a, hipStream_t stream) {
+  constexpr int lds = kLds4 + kLdsExtra;
+  static bool attr = hipFuncSetAttribute(reinterpret_cast<const void*>(k_gemm_w4<PERSIST, ORDER, FUSED, FRONT>),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess;
+  (void)attr;
+  hipLaunchKernelGGL((k_gemm_w4<PERSIST, ORDER, FUSED, FRONT>), dim3(grid), dim3(WNT), lds, stream, a);
 }
 
-// four-slot LDS ring kernel: EPI 1 (fast) when the output is bf16 with no bias, activation
-// or accumulation and C rows are 16-B vectors; persistent grid (g_w4_sched bit 0) then.
-// Diagnostics: sched bits 5-6 ablations, bit 9 s_memtime stamps (g_w4_dbg).
-static void w4r_attr(const void* f) { (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kRingLds); }
-static void w4p_attr(const void* f) { (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kPairLds); }
+template <int EPI, int PERSIST, int TA, int TB, int PAIR>
+static void launch_w4r(int grid, const W4Args& a, hipStream_t stream) {
+  constexpr int lds = PAIR ? kPairLds : kRingLds;
+  static bool attr = hipFuncSetAttribute(reinterpret_cast<const void*>(k_gemm_w4r<EPI, PERSIST, TA, TB, PAIR>),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess;
+  (void)attr;
+  hipLaunchKernelGGL((k_gemm_w4r<EPI, PERSIST, TA, TB, PAIR>), dim3(grid), dim3(WNT), lds, stream, a);
+}
 
+// K-major operand forms (ta or tb set; one workgroup per tile): generic or fast epilogue
+template <int PAIR>
+static void launch_w4r_kmajor(int ta, int tb, bool fast, int grid, const W4Args& a, hipStream_t stream) {
+  if (ta && tb) fast ? launch_w4r<1, 0, 1, 1, PAIR>(grid, a, stream) : launch_w4r<0, 0, 1, 1, PAIR>(grid, a, stream);
+  else if (ta) fast ? launch_w4r<1, 0, 1, 0, PAIR>(grid, a, stream) : launch_w4r<0, 0, 1, 0, PAIR>(grid, a, stream);
+  else fast ? launch_w4r<1, 0, 0, 1, PAIR>(grid, a, stream) : launch_w4r<0, 0, 0, 1, PAIR>(grid, a, stream);
+}
+
+// EPI 1 (fast) applies when the output is bf16 with no bias, activation or accumulation and
+// C rows are 16-B vectors; the persistent grid (sched bit 0) needs it.
 bool gemm_w4r_fast(const GemmArgs& g) {
   return g.out_bf16 && !g.accumulate && g.act == 0 && g.bias_kind == 0 && g.splitk == 1 && g.N % 8 == 0 && g.ldc % 8 == 0 &&
          ((uint64_t)g.C % 16) == 0 && (uint64_t)g.M * g.ldc * 2 < 0x7ffffff0ull;
 }
-
-void launch_gemm_nt_w4r(const GemmArgs& g, hipStream_t stream) { launch_gemm_ring(g, 0, 0, stream); }
 
 bool gemm_ring_ok(const GemmArgs& g, int ta, int tb) {
   if (g.splitk != 1 || g.K % WK || g.K < WK || g.lda % 8 || g.ldb % 8 || ((uint64_t)g.A % 16) || ((uint64_t)g.B % 16))
@@ -1228,47 +1115,8 @@ void launch_gemm_ring(const GemmArgs& g, int ta, int tb, hipStream_t stream, uin
   // explicit ring schedule (gemm_set_kernel(5) + sched bit 3) or the auto defaults
   const int sched = (g_w4_sched & 8) ? g_w4_sched : g_ring_sched;
   ++g_ring_launches;
-  static int cus = [] {
-    int dev = 0, n = 0;
-    (void)hipGetDevice(&dev);
-    return hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0 ? n : 256;
-  }();
-  static bool attr = [] {
-    // 4-slot ring: generic / fast / persistent / SwiGLU epilogues, diagnostics, K-major forms
-    w4r_attr(reinterpret_cast<const void*>(k_gemm_w4r<0, 0>));
-    w4r_attr(reinterpret_cast<const void*>(k_gemm_w4r<1, 0>));
-    w4r_attr(reinterpret_cast<const void*>(k_gemm_w4r<1, 1>));
-    w4r_attr(reinterpret_cast<const void*>(k_gemm_w4r<2, 0>));
-    w4r_attr(reinterpret_cast<const void*>(k_gemm_w4r<1, 0, 1>));
-    w4r_attr(reinterpret_cast<const void*>(k_gemm_w4r<1, 0, 2>));
-    w4r_attr(reinterpret_cast<const void*>(k_gemm_w4r<1, 0, 3>));
-    w4r_attr(reinterpret_cast<const void*>(k_gemm_w4r<1, 0, 4>));
-    w4r_attr(reinterpret_cast<const void*>(k_gemm_w4r<1, 0, 0, 1>));
-    w4r_attr(reinterpret_cast<const void*>(k_gemm_w4r<1, 1, 0, 1>));
-    w4r_attr(reinterpret_cast<const void*>(k_gemm_w4r<0, 0, 0, 0, 0, 1>));
-    w4r_attr(reinterpret_cast<const void*>(k_gemm_w4r<1, 0, 0, 0, 0, 1>));
-    w4r_attr(reinterpret_cast<const void*>(k_gemm_w4r<0, 0, 0, 0, 1, 1>));
-    w4r_attr(reinterpret_cast<const void*>(k_gemm_w4r<1, 0, 0, 0, 1, 1>));
-    w4r_attr(reinterpret_cast<const void*>(k_gemm_w4r<0, 0, 0, 0, 1, 0>));
-    w4r_attr(reinterpret_cast<const void*>(k_gemm_w4r<1, 0, 0, 0, 1, 0>));
-    // pair-slot ring
-    w4p_attr(reinterpret_cast<const void*>(k_gemm_w4r<0, 0, 0, 0, 0, 0, 1>));
-    w4p_attr(reinterpret_cast<const void*>(k_gemm_w4r<1, 0, 0, 0, 0, 0, 1>));
-    w4p_attr(reinterpret_cast<const void*>(k_gemm_w4r<2, 0, 0, 0, 0, 0, 1>));
-    w4p_attr(reinterpret_cast<const void*>(k_gemm_w4r<1, 1, 0, 0, 0, 0, 1>));
-    w4p_attr(reinterpret_cast<const void*>(k_gemm_w4r<2, 1, 0, 0, 0, 0, 1>));
-    w4p_attr(reinterpret_cast<const void*>(k_gemm_w4r<0, 0, 0, 0, 0, 1, 1>));
-    w4p_attr(reinterpret_cast<const void*>(k_gemm_w4r<1, 0, 0, 0, 0, 1, 1>));
-    w4p_attr(reinterpret_cast<const void*>(k_gemm_w4r<0, 0, 0, 0, 1, 0, 1>));
-    w4p_attr(reinterpret_cast<const void*>(k_gemm_w4r<1, 0, 0, 0, 1, 0, 1>));
-    w4p_attr(reinterpret_cast<const void*>(k_gemm_w4r<0, 0, 0, 0, 1, 1, 1>));
-    w4p_attr(reinterpret_cast<const void*>(k_gemm_w4r<1, 0, 0, 0, 1, 1, 1>));
-    return true;
-  }();
-  (void)attr;
   const int ntiles = gemm_w4_tiles(g.M, g.N);
-  W4Args a{g, g_w4_group_m, {}, g_w4_dbg, glu, ldglu};
-  a.nobar = g_pair_nobar;
+  W4Args a{g, g_w4_group_m, {}, glu, ldglu};
   const bool fast = gemm_w4r_fast(g);
   if (push_rows) {  // row blocks into peers' inboxes: the fast NT epilogue, whole tiles per block
     const int blocks = push_rows > 0 ? g.M / push_rows : 0;
@@ -1278,123 +1126,57 @@ void launch_gemm_ring(const GemmArgs& g, int ta, int tb, hipStream_t stream, uin
     for (int j = 0; j < blocks; ++j) a.push[j] = push[j];
   }
   const bool pair = sched & 16384;
+  // persistent instantiations take `grid`, every other one a workgroup per tile
   const bool persist = fast && (sched & 1);
-  const int grid = persist ? std::min(ntiles, cus) : ntiles;
+  const int grid = persist ? std::min(ntiles, device_cus()) : ntiles;
   if (glu) {  // SwiGLU epilogue (callers check gemm_w4r_fast and the glu layout first)
     if (!fast || ta || tb) throw std::invalid_argument("gemm ring: the SwiGLU epilogue needs the fast NT form");
-    if (pair && persist) hipLaunchKernelGGL((k_gemm_w4r<2, 1, 0, 0, 0, 0, 1>), dim3(grid), dim3(WNT), kPairLds, stream, a);
-    else if (pair) hipLaunchKernelGGL((k_gemm_w4r<2, 0, 0, 0, 0, 0, 1>), dim3(ntiles), dim3(WNT), kPairLds, stream, a);
-    else hipLaunchKernelGGL((k_gemm_w4r<2, 0>), dim3(ntiles), dim3(WNT), kRingLds, stream, a);
-    return;
-  }
-  if ((ta || tb) && pair && (tb || g_pair_ta)) {
-    // K-major operands on the pair-slot ring: dX = dY W (B), dW = dY^T X (A and B: no
-    // transposes); K-major A alone only on request (CCMPI_PAIR_TA)
-    const int v = (ta ? 2 : 0) + (tb ? 1 : 0) + (fast ? 4 : 0);
-    switch (v) {
-      case 1: hipLaunchKernelGGL((k_gemm_w4r<0, 0, 0, 0, 0, 1, 1>), dim3(ntiles), dim3(WNT), kPairLds, stream, a); break;
-      case 5: hipLaunchKernelGGL((k_gemm_w4r<1, 0, 0, 0, 0, 1, 1>), dim3(ntiles), dim3(WNT), kPairLds, stream, a); break;
-      case 2: hipLaunchKernelGGL((k_gemm_w4r<0, 0, 0, 0, 1, 0, 1>), dim3(ntiles), dim3(WNT), kPairLds, stream, a); break;
-      case 6: hipLaunchKernelGGL((k_gemm_w4r<1, 0, 0, 0, 1, 0, 1>), dim3(ntiles), dim3(WNT), kPairLds, stream, a); break;
-      case 3: hipLaunchKernelGGL((k_gemm_w4r<0, 0, 0, 0, 1, 1, 1>), dim3(ntiles), dim3(WNT), kPairLds, stream, a); break;
-      default: hipLaunchKernelGGL((k_gemm_w4r<1, 0, 0, 0, 1, 1, 1>), dim3(ntiles), dim3(WNT), kPairLds, stream, a); break;
-    }
-    return;
-  }
-  if (ta || tb) {  // K-major operands on the 4-slot ring: non-persistent, no diagnostics
-    const int v = (ta ? 2 : 0) + (tb ? 1 : 0) + (fast ? 4 : 0);
-    switch (v) {
-      case 1: hipLaunchKernelGGL((k_gemm_w4r<0, 0, 0, 0, 0, 1>), dim3(ntiles), dim3(WNT), kRingLds, stream, a); break;
-      case 5: hipLaunchKernelGGL((k_gemm_w4r<1, 0, 0, 0, 0, 1>), dim3(ntiles), dim3(WNT), kRingLds, stream, a); break;
-      case 2: hipLaunchKernelGGL((k_gemm_w4r<0, 0, 0, 0, 1, 0>), dim3(ntiles), dim3(WNT), kRingLds, stream, a); break;
-      case 6: hipLaunchKernelGGL((k_gemm_w4r<1, 0, 0, 0, 1, 0>), dim3(ntiles), dim3(WNT), kRingLds, stream, a); break;
-      case 3: hipLaunchKernelGGL((k_gemm_w4r<0, 0, 0, 0, 1, 1>), dim3(ntiles), dim3(WNT), kRingLds, stream, a); break;
-      default: hipLaunchKernelGGL((k_gemm_w4r<1, 0, 0, 0, 1, 1>), dim3(ntiles), dim3(WNT), kRingLds, stream, a); break;
-    }
-    return;
-  }
-  const int abl = (sched >> 5) & 3;
-  if (pair) {
-    // pair-slot ring: whole-line DMA pieces, 64-deep slots (bit 0: persistent grid)
-    if (persist) hipLaunchKernelGGL((k_gemm_w4r<1, 1, 0, 0, 0, 0, 1>), dim3(grid), dim3(WNT), kPairLds, stream, a);
-    else if (fast) hipLaunchKernelGGL((k_gemm_w4r<1, 0, 0, 0, 0, 0, 1>), dim3(ntiles), dim3(WNT), kPairLds, stream, a);
-    else hipLaunchKernelGGL((k_gemm_w4r<0, 0, 0, 0, 0, 0, 1>), dim3(ntiles), dim3(WNT), kPairLds, stream, a);
-  } else if (!fast) {
-    hipLaunchKernelGGL((k_gemm_w4r<0, 0>), dim3(grid), dim3(WNT), kRingLds, stream, a);
-  } else if (sched & 512) {  // diagnostic: s_memtime stamps
-    if (persist) hipLaunchKernelGGL((k_gemm_w4r<1, 1, 0, 1>), dim3(grid), dim3(WNT), kRingLds, stream, a);
-    else hipLaunchKernelGGL((k_gemm_w4r<1, 0, 0, 1>), dim3(grid), dim3(WNT), kRingLds, stream, a);
-  } else if (sched & 8192) {
-    // diagnostic: whole-cache-line DMA pieces (ABL 4, wrong results)
-    hipLaunchKernelGGL((k_gemm_w4r<1, 0, 4>), dim3(grid), dim3(WNT), kRingLds, stream, a);
-  } else if (abl == 1) {
-    hipLaunchKernelGGL((k_gemm_w4r<1, 0, 1>), dim3(grid), dim3(WNT), kRingLds, stream, a);
-  } else if (abl == 2) {
-    hipLaunchKernelGGL((k_gemm_w4r<1, 0, 2>), dim3(grid), dim3(WNT), kRingLds, stream, a);
-  } else if (abl == 3) {
-    hipLaunchKernelGGL((k_gemm_w4r<1, 0, 3>), dim3(grid), dim3(WNT), kRingLds, stream, a);
-  } else if (persist) {
-    hipLaunchKernelGGL((k_gemm_w4r<1, 1>), dim3(grid), dim3(WNT), kRingLds, stream, a);
+    if (pair && persist) launch_w4r<2, 1, 0, 0, 1>(grid, a, stream);
+    else if (pair) launch_w4r<2, 0, 0, 0, 1>(ntiles, a, stream);
+    else launch_w4r<2, 0, 0, 0, 0>(ntiles, a, stream);
+  } else if (ta || tb) {
+    // K-major operands, never persistent.  On the pair-slot ring: dX = dY W (B), dW = dY^T X
+    // (A and B: no transposes); K-major A alone only on request (CCMPI_PAIR_TA), else the
+    // 4-slot ring
+    if (pair && (tb || g_pair_ta)) launch_w4r_kmajor<1>(ta, tb, fast, ntiles, a, stream);
+    else launch_w4r_kmajor<0>(ta, tb, fast, ntiles, a, stream);
+  } else if (pair) {
+    // pair-slot ring: whole-line DMA pieces, 64-deep slots
+    if (persist) launch_w4r<1, 1, 0, 0, 1>(grid, a, stream);
+    else if (fast) launch_w4r<1, 0, 0, 0, 1>(ntiles, a, stream);
+    else launch_w4r<0, 0, 0, 0, 1>(ntiles, a, stream);
   } else {
-    hipLaunchKernelGGL((k_gemm_w4r<1, 0>), dim3(grid), dim3(WNT), kRingLds, stream, a);
+    if (persist) launch_w4r<1, 1, 0, 0, 0>(grid, a, stream);
+    else if (fast) launch_w4r<1, 0, 0, 0, 0>(ntiles, a, stream);
+    else launch_w4r<0, 0, 0, 0, 0>(ntiles, a, stream);
   }
 }
 
 void launch_gemm_nt_w4(const GemmArgs& g, hipStream_t stream) {
-  static int cus = [] {
-    int dev = 0, n = 0;
-    (void)hipGetDevice(&dev);
-    return hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0 ? n : 256;
-  }();
-  const int ntiles = ((g.M + WM - 1) / WM) * ((g.N + WNB - 1) / WNB);
-  W4Args a{g, g_w4_group_m, {}, nullptr};
+  if (g_w4_sched & 8) return launch_gemm_ring(g, 0, 0, stream);
+  const int ntiles = gemm_w4_tiles(g.M, g.N);
+  W4Args a{g, g_w4_group_m};
   const bool persist = g_w4_sched & 1;
-  const int grid = persist ? std::min(ntiles, cus) : ntiles;
-  static bool attr = [] {
-    w4_attr(reinterpret_cast<const void*>(k_gemm_w4<0, 0>));
-    w4_attr(reinterpret_cast<const void*>(k_gemm_w4<1, 0>));
-    w4_attr(reinterpret_cast<const void*>(k_gemm_w4<0, 1>));
-    w4_attr(reinterpret_cast<const void*>(k_gemm_w4<1, 1>));
-    w4_attr(reinterpret_cast<const void*>(k_gemm_w4<0, 0, 0, 1>));
-    w4_attr(reinterpret_cast<const void*>(k_gemm_w4<1, 0, 0, 1>));
-    return true;
-  }();
-  (void)attr;
-  if (g_w4_sched & 8) {
-    launch_gemm_nt_w4r(g, stream);
+  const int grid = persist ? std::min(ntiles, device_cus()) : ntiles;
+  if (g_w4_sched & 4) {  // front-loaded DMA
+    if (persist) launch_w4<1, 0, 0, 1>(grid, a, stream);
+    else launch_w4<0, 0, 0, 1>(grid, a, stream);
     return;
   }
-  if (g_w4_sched & 4) {
-    if (persist) hipLaunchKernelGGL((k_gemm_w4<1, 0, 0, 1>), dim3(grid), dim3(WNT), kLds4 + kLdsExtra, stream, a);
-    else hipLaunchKernelGGL((k_gemm_w4<0, 0, 0, 1>), dim3(grid), dim3(WNT), kLds4 + kLdsExtra, stream, a);
-    return;
-  }
-  switch (g_w4_sched & 3) {
-    case 0: hipLaunchKernelGGL((k_gemm_w4<0, 0>), dim3(grid), dim3(WNT), kLds4 + kLdsExtra, stream, a); break;
-    case 1: hipLaunchKernelGGL((k_gemm_w4<1, 0>), dim3(grid), dim3(WNT), kLds4 + kLdsExtra, stream, a); break;
-    case 2: hipLaunchKernelGGL((k_gemm_w4<0, 1>), dim3(grid), dim3(WNT), kLds4 + kLdsExtra, stream, a); break;
-    default: hipLaunchKernelGGL((k_gemm_w4<1, 1>), dim3(grid), dim3(WNT), kLds4 + kLdsExtra, stream, a); break;
+  switch (g_w4_sched & 3) {  // bit 0 persistent, bit 1 MFMA-first order
+    case 0: launch_w4<0, 0>(grid, a, stream); break;
+    case 1: launch_w4<1, 0>(grid, a, stream); break;
+    case 2: launch_w4<0, 1>(grid, a, stream); break;
+    default: launch_w4<1, 1>(grid, a, stream); break;
   }
 }
 
 int gemm_w4_tiles(int M, int N) { return ((M + WM - 1) / WM) * ((N + WNB - 1) / WNB); }
 
 void launch_gemm_nt_w4_fused(const GemmArgs& g, const FusedArgs& f, hipStream_t stream) {
-  static int cus = [] {
-    int dev = 0, n = 0;
-    (void)hipGetDevice(&dev);
-    return hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0 ? n : 256;
-  }();
   // one workgroup per tile (the persistent form spills registers with the fused epilogue)
-  static bool attr = [] {
-    w4_attr(reinterpret_cast<const void*>(k_gemm_w4<0, 0, 1>));
-    return true;
-  }();
-  (void)attr;
-  (void)cus;
-  const int ntiles = gemm_w4_tiles(g.M, g.N);
-  W4Args a{g, g_w4_group_m, f, nullptr};
-  hipLaunchKernelGGL((k_gemm_w4<0, 0, 1>), dim3(ntiles), dim3(WNT), kLds4 + kLdsExtra, stream, a);
+  W4Args a{g, g_w4_group_m, f};
+  launch_w4<0, 0, 1>(gemm_w4_tiles(g.M, g.N), a, stream);
 }
 
 void launch_fused_wait(const FusedArgs& f, int tiles, hipStream_t stream) {

@@ -156,7 +156,7 @@ __global__ void __launch_bounds__(NT) k_grouped_gemm_nt(GroupedArgs a) {
   // MFMA operands for the direct epilogue.
   floatx4 acc[4][4];
   const NtSrc src{a.A, Bg, a.lda, a.ldb, bm, row_end, bn, a.N, a.K, 0, GLDS ? a.K / BK : (a.K + BK - 1) / BK};
-  if constexpr (GLDS) nt_loop_glds<true>(src, smem, acc, wave, lane);
+  if constexpr (GLDS) nt_loop_glds(src, smem, acc, wave, lane);
   else nt_loop_regs<true>(src, smem, acc, wave, t);
 
   const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;

@@ -28,7 +28,7 @@ def _ref(a, b, bias=None, act=None, alpha=1.0):
 
 @pytest.mark.parametrize("M,N,K", [(1, 1, 8), (16, 16, 32), (128, 128, 64), (130, 70, 72), (2048, 768, 64),
                                    (32768, 768, 72), (1000, 300, 40), (513, 1000, 128), (300, 7, 8),
-                                   (4096, 768, 768), (32768, 384, 768), (777, 1000, 520)])
+                                   (4096, 768, 768), (32768, 384, 768), (777, 1000, 520), (130, 76, 64)])
 def test_gemm_nt_shapes(M, N, K):
     from collective_communication_mpi_amd.ops import gemm_nt
 
@@ -87,7 +87,7 @@ def test_gemm256_epilogue(gemm256, act):
 @pytest.mark.parametrize("sched", [0, 1, 3, 4, 5, 8, 9, 8 | 16384, 9 | 16384],
                          ids=["w4", "w4p", "w4po", "w4f", "w4pf", "ring", "ringp", "ringpair", "ringpairp"])
 @pytest.mark.parametrize("M,N,K", [(256, 256, 64), (256, 256, 128), (300, 520, 256), (777, 1000, 512),
-                                   (2048, 2048, 4096), (1, 8, 192), (4096, 768, 768)])
+                                   (2048, 2048, 4096), (1, 8, 192), (4096, 768, 768), (260, 332, 128)])
 def test_gemm_w4_shapes(sched, M, N, K):
     """Four-wave 256x256 kernels (gemm_w4.hip), every schedule variant incl. the LDS ring,
     against an fp32 reference; bias + bf16 out and accumulate on one shape."""
