@@ -12,6 +12,7 @@ void register_wgrad_ops(pybind11::module_& m);
 void register_swiglu_ops(pybind11::module_& m);
 void register_grouped_gemm_ops(pybind11::module_& m);
 void register_moe_gate_ops(pybind11::module_& m);
+void register_moe_router_ops(pybind11::module_& m);
 
 void register_ops(pybind11::module_& m) {
   register_layout_ops(m);
@@ -22,6 +23,7 @@ void register_ops(pybind11::module_& m) {
   register_swiglu_ops(m);
   register_grouped_gemm_ops(m);
   register_moe_gate_ops(m);
+  register_moe_router_ops(m);
 }
 
 }  // namespace dev

@@ -737,3 +737,189 @@ def moe_gate(logits: torch.Tensor, top_k: int, renormalize: bool = True):
     statistics of a load-balancing loss (``RoutedMoE.aux_loss``)."""
     moe_gate_validate(logits, top_k)
     return _MoEGate.apply(logits, int(top_k), bool(renormalize))
+
+
+# ---------------------------------------------------------------------------
+# router logits on the matrix cores (csrc/device/moe_router.hip)
+# ---------------------------------------------------------------------------
+def split_bf16x3(w: torch.Tensor, planes: int = 3, transpose: bool = False, out: Optional[torch.Tensor] = None, *,
+                 concat=None, pad: int = 8) -> torch.Tensor:
+    """An fp32 matrix ``w`` [R, C] as bf16 planes whose sum is ``w``: plane 0 is ``bf16(w)``, plane
+    i is ``bf16(w - the earlier planes)``, every subtraction in fp32 and every rounding to nearest
+    even; bit for bit ``p0 = w.bfloat16(); p1 = (w - p0.float()).bfloat16(); p2 = (w - p0.float()
+    - p1.float()).bfloat16()``.  Three planes hold a finite fp32 number exactly.  Returns bf16
+    ``[planes, R, C]``, or ``[planes, C, R]`` with ``transpose``.
+
+    ``concat``: a sequence of 1 to 4 plane numbers, e.g. ``(0, 0, 1)``; the result is then 2-D, the
+    named planes side by side along the last axis, ``[R, len(concat) * C']`` (``[C, len(concat) *
+    R']`` with ``transpose``), every block's width rounded up to a multiple of ``pad`` and the
+    padding zero: the operand of a GEMM that reduces over the planes in one pass.  ``planes`` is
+    ignored then.  Inputs must be finite.  One kernel, no host synchronisation."""
+    if w.dtype != torch.float32:
+        raise TypeError(f"split_bf16x3 expects an fp32 tensor, got {w.dtype}")
+    if w.dim() != 2 or not w.is_contiguous():
+        raise ValueError("split_bf16x3 expects a contiguous 2-D tensor")
+    R, C = w.shape
+    slow, fast = (C, R) if transpose else (R, C)
+    if concat is None:
+        if not 1 <= int(planes) <= 3:
+            raise ValueError(f"split_bf16x3: planes must be 1, 2 or 3, got {planes}")
+        slots = list(range(int(planes)))
+        shape, slot_stride, ld, fpad = (len(slots), slow, fast), slow * fast, fast, fast
+    else:
+        slots = [int(p) for p in concat]
+        if not 1 <= len(slots) <= 4 or any(p < 0 or p > 2 for p in slots) or int(pad) < 1:
+            raise ValueError("split_bf16x3: concat names 1 to 4 planes out of 0, 1, 2; pad >= 1")
+        fpad = (fast + int(pad) - 1) // int(pad) * int(pad)
+        shape, slot_stride, ld = (slow, len(slots) * fpad), fpad, len(slots) * fpad
+    if not w.is_cuda:
+        raise ValueError("split_bf16x3 runs on the GPU: w is on " + str(w.device))
+    if out is None:
+        out = torch.empty(shape, dtype=torch.bfloat16, device=w.device)
+    elif out.dtype != torch.bfloat16 or tuple(out.shape) != tuple(shape) or not out.is_contiguous() \
+            or out.device != w.device:
+        raise ValueError(f"split_bf16x3: out must be a contiguous bf16 {tuple(shape)} tensor on w's device")
+    if R and C:
+        _D().split_bf16x3(w.data_ptr(), out.data_ptr(), R, C, len(slots), sum(p << (2 * s) for s, p in enumerate(slots)),
+                          slot_stride, ld, fpad, bool(transpose), _stream(w))
+    elif out.numel():
+        out.zero_()
+    return out
+
+
+def moe_router_logits_validate(x, router):
+    """Argument rules of ``moe_router_logits`` that need no GPU; raises TypeError (dtypes) /
+    ValueError (shapes, strides, alignment) and returns ``(T, D, E)``: ``x`` [T, D] bf16 with unit
+    column stride, a row stride that is a multiple of 8 and a 16-byte aligned base, ``D % 8 == 0``,
+    ``0 <= T < 2^31 - 64``; ``router`` [E, D] fp32 and contiguous, ``1 <= E <= 256``."""
+    if x.dtype != torch.bfloat16:
+        raise TypeError(f"moe_router_logits expects bf16 activations, got {x.dtype}")
+    if router.dtype != torch.float32:
+        raise TypeError(f"moe_router_logits expects an fp32 router, got {router.dtype}")
+    if x.dim() != 2 or router.dim() != 2:
+        raise ValueError(f"moe_router_logits: x must be [T, D] and router [E, D], got {tuple(x.shape)} and "
+                         f"{tuple(router.shape)}")
+    T, D = x.shape
+    E = router.shape[0]
+    if router.shape[1] != D:
+        raise ValueError(f"moe_router_logits: x has D = {D}, the router {router.shape[1]}")
+    if D < 8 or D % 8:
+        raise ValueError(f"moe_router_logits: D must be a positive multiple of 8, got {D}")
+    if E < 1 or E > MOE_GATE_MAX_EXPERTS:
+        raise ValueError(f"moe_router_logits: the number of experts must be in [1, {MOE_GATE_MAX_EXPERTS}], got {E}")
+    if T >= (1 << 31) - MOE_GATE_CHUNK:
+        raise ValueError("moe_router_logits: T must be below 2^31 - 64")
+    if not router.is_contiguous():
+        raise ValueError("moe_router_logits: the router must be contiguous")
+    if x.stride(1) != 1 or (T > 1 and (x.stride(0) % 8 or x.stride(0) < D)):
+        raise ValueError("moe_router_logits: x needs unit column stride and a row stride that is a multiple of 8")
+    if x.data_ptr() % 16:
+        raise ValueError("moe_router_logits: x must be 16-byte aligned")
+    return int(T), int(D), int(E)
+
+
+def _router_planes_check(planes, E: int, D: int, device) -> None:
+    if planes.dtype != torch.bfloat16:
+        raise TypeError("moe_router_logits: planes must be bf16 (split_bf16x3 of the router)")
+    if tuple(planes.shape) != (3, E, D) or not planes.is_contiguous() or planes.data_ptr() % 16 \
+            or planes.device != device:
+        raise ValueError(f"moe_router_logits: planes must be a contiguous, 16-byte aligned [3, {E}, {D}] tensor on "
+                         "x's device")
+
+
+def moe_router_logits_forward(x: torch.Tensor, router: torch.Tensor, planes: Optional[torch.Tensor] = None,
+                              out: Optional[torch.Tensor] = None, row_tile: Optional[int] = None) -> torch.Tensor:
+    """``logits`` [T, E] fp32 ``= x . router^T`` on the matrix cores (``k_moe_router_logits``): the
+    fp32 ``router`` [E, D] enters as its three bf16 planes (``split_bf16x3``; pass an earlier
+    result as ``planes`` to skip the split), ``x`` [T, D] bf16 is read once, every product is exact
+    and only the fp32 accumulation rounds.  One element is accumulated in an order that depends on
+    D alone: no split-K, no atomics, so the result is bitwise reproducible and a token's logits do
+    not depend on the other rows (``forward(x[:n]) == forward(x)[:n]``).  ``row_tile`` (128, 64 or
+    32 rows per workgroup; None: the largest that gives every CU a workgroup) is a scheduling
+    choice for tests and benchmarks: the bits do not depend on it.  Plain tensors, no autograd;
+    no host synchronisation, and with ``planes`` and ``out`` no allocation."""
+    T, D, E = moe_router_logits_validate(x, router)
+    if not x.is_cuda or router.device != x.device:
+        raise ValueError("moe_router_logits: x and the router must be on one GPU")
+    if planes is None:
+        planes = split_bf16x3(router)
+    _router_planes_check(planes, E, D, x.device)
+    if out is None:
+        out = torch.empty((T, E), dtype=torch.float32, device=x.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (T, E) or not out.is_contiguous() or out.device != x.device:
+        raise ValueError(f"moe_router_logits: out must be a contiguous fp32 [{T}, {E}] tensor on x's device")
+    if row_tile not in (None, 32, 64, 128):
+        raise ValueError(f"moe_router_logits: row_tile must be None, 32, 64 or 128, got {row_tile!r}")
+    if T:
+        _D().moe_router_logits_fwd(x.data_ptr(), planes.data_ptr(), out.data_ptr(), T, E, D, x.stride(0) if T > 1 else D,
+                                   int(row_tile or 0), _stream(x))
+    return out
+
+
+def moe_router_logits_backward(dlogits: torch.Tensor, x: torch.Tensor, router_planes: torch.Tensor,
+                               need_dx: bool = True, need_drouter: bool = True):
+    """``(dx, drouter)`` of ``moe_router_logits_forward``: ``dx`` [T, D] bf16 ``= dlogits @ router``
+    and ``drouter`` [E, D] fp32 ``= dlogits^T @ x`` (None where not needed), without an fp32 tensor
+    of size [T, D].  ``dlogits`` [T, E] fp32 is split into bf16 planes d0, d1, d2 by one
+    ``split_bf16x3`` launch.  ``dx`` is one ``gemm_nt`` over ``[d0 | d0 | d1] . [R0 | R1 | R0]^T``
+    (``R`` the router planes; the dropped terms are below 2^-16 relative, under the bf16 rounding
+    of the result); ``drouter`` is one ``gemm_tn`` of ``[d0 | d1 | d2]`` against ``x`` through the
+    workspace reduction, its three [E, D] blocks summed in plane order 2, 1, 0.  No atomics."""
+    if dlogits.dtype != torch.float32:
+        raise TypeError(f"moe_router_logits_backward expects fp32 dlogits, got {dlogits.dtype}")
+    if x.dtype != torch.bfloat16:
+        raise TypeError(f"moe_router_logits_backward expects bf16 activations, got {x.dtype}")
+    if dlogits.dim() != 2 or x.dim() != 2 or dlogits.shape[0] != x.shape[0]:
+        raise ValueError("moe_router_logits_backward: dlogits must be [T, E] and x [T, D]")
+    T, E = dlogits.shape
+    D = x.shape[1]
+    if not x.is_cuda or dlogits.device != x.device:
+        raise ValueError("moe_router_logits_backward: dlogits and x must be on one GPU")
+    _router_planes_check(router_planes, E, D, x.device)
+    if x.stride(1) != 1 or (T > 1 and x.stride(0) % 8) or x.data_ptr() % 16:
+        raise ValueError("moe_router_logits_backward: x needs unit column stride, a row stride that is a multiple of "
+                         "8 and a 16-byte aligned base")
+    if T == 0:
+        return (torch.empty((0, D), dtype=torch.bfloat16, device=x.device) if need_dx else None,
+                torch.zeros((E, D), dtype=torch.float32, device=x.device) if need_drouter else None)
+    if not (need_dx or need_drouter):
+        return None, None
+    Ep = (E + 7) // 8 * 8
+    # one split for both products: dx reads [d0 | d0 | d1], drouter [d0 | d1 | d2]
+    slots = (0, 0, 1, 2) if need_dx and need_drouter else (0, 0, 1) if need_dx else (0, 1, 2)
+    dl = split_bf16x3(dlogits.contiguous(), concat=slots, pad=8)
+    dx = drouter = None
+    if need_dx:
+        alloc = torch.zeros if Ep != E else torch.empty
+        rt = alloc((D, 3 * Ep), dtype=torch.bfloat16, device=x.device)
+        for s, p in enumerate((0, 1, 0)):
+            transpose(router_planes[p], out=rt[:, s * Ep:s * Ep + E])
+        dx = gemm_nt(dl[:, :3 * Ep], rt, out_dtype=torch.bfloat16, splitk=1)
+    if need_drouter:
+        part = gemm_tn(dl[:, (len(slots) - 3) * Ep:], x, workspace=True)  # [3 E', D]
+        drouter = (part[2 * Ep:2 * Ep + E] + part[Ep:Ep + E]) + part[:E]
+    return dx, drouter
+
+
+class _MoERouterLogits(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, router):
+        planes = split_bf16x3(router)
+        ctx.save_for_backward(x, planes)
+        return moe_router_logits_forward(x, router, planes=planes)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dlogits):
+        x, planes = ctx.saved_tensors
+        return moe_router_logits_backward(dlogits, x, planes, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+
+
+def moe_router_logits(x: torch.Tensor, router: torch.Tensor) -> torch.Tensor:
+    """Differentiable ``moe_router_logits_forward``: ``x`` [T, D] bf16 and the fp32 ``router``
+    [E, D] give fp32 ``logits`` [T, E], as exact as an fp32 GEMM, on the bf16 matrix cores.
+    Autograd keeps ``x`` as the bf16 tensor it was given and the router's three bf16 planes; no
+    fp32 copy of the activations exists in the forward or the backward
+    (``moe_router_logits_backward``), and gradients are computed only for the inputs that ask."""
+    moe_router_logits_validate(x, router)
+    return _MoERouterLogits.apply(x, router)

@@ -144,6 +144,12 @@ class RoutedMoE(torch.nn.Module):
     backward); ``gate="torch"`` is the chain of torch ops.  The two agree up to fp32 rounding,
     and on ties between logits the fused gate takes the lower expert index.
 
+    ``router_logits="mfma"`` computes the logits with ``ops.moe_router_logits``: the fp32 router
+    as three bf16 planes on the matrix cores, one pass over ``x``, and no fp32 copy of ``x`` kept
+    for the backward; ``"torch"`` (the default) is ``x.float() @ router.t()``.  Both gates take
+    either result unchanged.  The two settings agree up to fp32 rounding (they sum in different
+    orders) and may pick different experts where two logits are closer than that.
+
     After a forward ``aux_loss`` is the Switch load-balancing loss of this rank's tokens,
     ``E * sum_e f_e P_e`` with ``f_e`` the share of the T * K selections that chose expert e
     (detached) and ``P_e`` the mean router probability of e; 1 at perfect balance, 0 when
@@ -152,7 +158,7 @@ class RoutedMoE(torch.nn.Module):
 
     def __init__(self, group, d_model: int, d_ff: int, num_experts: int, top_k: int, capacity: int,
                  renormalize: bool = True, dtype=torch.bfloat16, expert_capacity=None, gate: str = "torch",
-                 aux_loss_coef: float = 0.0):
+                 aux_loss_coef: float = 0.0, router_logits: str = "torch"):
         super().__init__()
         dev = _dev(group)
         if num_experts < 1 or num_experts % dev.size:
@@ -164,6 +170,8 @@ class RoutedMoE(torch.nn.Module):
             raise ValueError("RoutedMoE: capacity must be at least one row")
         if gate not in ("torch", "fused"):
             raise ValueError(f"RoutedMoE: gate must be 'torch' or 'fused', got {gate!r}")
+        if router_logits not in ("torch", "mfma"):
+            raise ValueError(f"RoutedMoE: router_logits must be 'torch' or 'mfma', got {router_logits!r}")
         if expert_capacity is not None:
             expert_capacity = int(expert_capacity)
             if expert_capacity < 1:
@@ -174,6 +182,7 @@ class RoutedMoE(torch.nn.Module):
         self.group, self.num_experts, self.top_k, self.capacity = dev, num_experts, top_k, int(capacity)
         self.renormalize = renormalize
         self.expert_capacity, self.gate, self.aux_loss_coef = expert_capacity, gate, float(aux_loss_coef)
+        self.router_logits = router_logits
         self.aux_loss = None
         self.router = torch.nn.Parameter(torch.randn(num_experts, d_model, device=dev.device, dtype=torch.float32)
                                          / math.sqrt(d_model))
@@ -188,7 +197,10 @@ class RoutedMoE(torch.nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         T = x.shape[0]
-        logits = x.float() @ self.router.t()
+        if self.router_logits == "mfma":
+            logits = ops.moe_router_logits(x, self.router)
+        else:
+            logits = x.float() @ self.router.t()
         if self.gate == "fused":
             w, idx, prob_sum, expert_tokens = ops.moe_gate(logits, self.top_k, self.renormalize)
         else:
