@@ -777,9 +777,12 @@ void gemm_tn(uint64_t A, uint64_t B, uint64_t C, int M, int N1, int N2, int lda,
   if (N1 <= 0 || N2 <= 0 || M <= 0) return;
   if (csplit <= 0 || csplit >= N2) {
     csplit = N2;  // no second destination
-  } else if (C2 == 0 || csplit % 4 || ldc2 % 4 || (C2 % 16) || splitk < 2 || workspace == 0) {
+  } else if (C2 == 0 || csplit % 4 || ldc2 % 4 || (C2 % 16) || ldc % 4 || (C % 16) || (workspace % 16) || splitk < 2 ||
+             workspace == 0) {
+    // (only the workspace reduction splits the columns: with a C it cannot write as 16-B
+    // vectors the kernel would store all N2 columns through ldc, past the [N1, csplit] output)
     throw std::invalid_argument("ccmpi gemm_tn: a column-split output needs split-K with a workspace, "
-                                "csplit % 4 == 0 and a 16-B aligned second output");
+                                "csplit % 4 == 0 and 16-B aligned rows in both outputs");
   }
   if (N1 % 8 || N2 % 8 || lda % 8 || ldb % 8 || (A % 16) || (B % 16))
     throw std::invalid_argument("ccmpi gemm_tn: N1, N2, lda, ldb must be multiples of 8 and A/B 16-B aligned");

@@ -41,6 +41,14 @@ def gemm_nt(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None
 
     a: [M, K] bf16 row-major (row stride may exceed K), b: [N, K] bf16; K % 8 == 0.
     bias: [N] fp32 or bf16.  out: [M, N] bf16 or fp32 (fp32 accumulate inside).
+
+    a and b may be views of larger buffers (column windows, row slices) as long as they start
+    16-B aligned and their row strides are multiples of 8 elements; anything else raises
+    ValueError.  What lies around them never reaches a result.  ``out`` may be any view with
+    unit column stride: a misaligned start, an odd row stride or N % 8 != 0 take the
+    per-element stores, and nothing outside ``[M, N]`` is written.  A bf16 output is one
+    round-to-nearest-even of the fp32 result (of result + previous contents with
+    ``accumulate``).  ``splitk`` > 1 needs an fp32 output and no activation (ValueError).
     """
     if a.dtype != torch.bfloat16 or b.dtype != torch.bfloat16:
         raise TypeError("gemm_nt expects bf16 operands")
@@ -85,8 +93,17 @@ def gemm_tn(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None
     overwritten) the rest, straight from the split-K reduction (one GEMM over a
     row-concatenated operand ``b = [X | Y]`` gives ``a^T X`` and ``a^T Y``).
 
+    Both outputs need 16-B aligned rows then (start and row stride): only the reduction
+    pass splits the columns, and it writes 16-B vectors.
+
     ``workspace``: split-K partials through a workspace + one reduction pass (True)
-    or fp32 atomics into ``out`` (False); default by output size."""
+    or fp32 atomics into ``out`` (False); default by output size.
+
+    a, b: bf16 with unit column stride, 16-B aligned start and rows (row strides may exceed
+    N1 / N2: column windows and row slices of larger buffers are fine), N1 % 8 == N2 % 8 == 0;
+    M is free, rows at and past M are never read into a result.  Without ``tail``, ``out``
+    may be any fp32 view with unit column stride (a misaligned start or an odd row stride
+    takes the per-element epilogue); nothing outside ``[N1, N2]`` is written."""
     if a.dtype != torch.bfloat16 or b.dtype != torch.bfloat16:
         raise TypeError("gemm_tn expects bf16 operands")
     if a.dim() != 2 or b.dim() != 2 or a.shape[0] != b.shape[0] or a.stride(1) != 1 or b.stride(1) != 1:
@@ -103,6 +120,9 @@ def gemm_tn(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None
             raise ValueError("gemm_tn tail must be fp32 [N1, N2 - out cols], 16-B aligned rows, out cols % 4 == 0")
         if out.dtype != torch.float32 or out.shape[0] != N1 or out.stride(1) != 1:
             raise ValueError("gemm_tn output must be fp32 [N1, c] with unit column stride")
+        if out.stride(0) % 4 or out.data_ptr() % 16:
+            raise ValueError("gemm_tn: with a tail, out needs 16-B aligned rows too (the split-K reduction "
+                             "writes both as 16-B vectors)")
     elif out is None:
         if accumulate:
             raise ValueError("accumulate needs an output tensor")
