@@ -447,13 +447,11 @@ def grouped_gemm_nt(x: torch.Tensor, w: torch.Tensor, counts: torch.Tensor, out:
     return out
 
 
-def grouped_gemm_tn(dy: torch.Tensor, x: torch.Tensor, counts: torch.Tensor, out: Optional[torch.Tensor] = None,
-                    alpha: float = 1.0) -> torch.Tensor:
-    """Weight gradients of ``grouped_gemm_nt``: ``out[g] = alpha * dy[rows of g].T @ x[rows of g]``,
-    fp32 ``[G, N, K]`` (dy [cap, N], x [cap, K] bf16, same row rules).  Both operands are read
-    row-major through ds_read_b64_tr_b16; rows outside an expert are masked at the load (they
-    may hold anything, NaN included); an expert with no rows gets zeros.  One workgroup per
-    (expert, 128 x 128 tile) walks the expert's rows in order: deterministic, no atomics."""
+def grouped_tn_validate(dy, x, counts, out=None):
+    """Argument rules of ``grouped_gemm_tn`` that need no GPU; raises TypeError (dtypes) /
+    ValueError (shapes, strides, alignment) and returns ``(cap, G, N, K)``.  ``dy`` [cap, N] and
+    ``x`` [cap, K] follow the forward's operand rules (unit inner stride, 16-B aligned rows);
+    ``out`` is fp32 ``[G, N, K]`` with unit inner stride, 16-B aligned rows and expert blocks."""
     if dy.dtype != torch.bfloat16 or x.dtype != torch.bfloat16:
         raise TypeError("grouped_gemm_tn expects bf16 operands")
     if dy.dim() != 2 or x.dim() != 2 or dy.shape[0] != x.shape[0] or dy.stride(1) != 1 or x.stride(1) != 1:
@@ -469,10 +467,30 @@ def grouped_gemm_tn(dy: torch.Tensor, x: torch.Tensor, counts: torch.Tensor, out
     K = x.shape[1]
     if N < 8 or K < 8 or N % 8 or K % 8:
         raise ValueError(f"grouped_gemm_tn: N ({N}) and K ({K}) must be positive multiples of 8")
+    if cap > 1 and (dy.stride(0) % 8 or x.stride(0) % 8):
+        raise ValueError("grouped_gemm_tn: row strides must be multiples of 8 elements (16 bytes)")
+    if dy.data_ptr() % 16 or x.data_ptr() % 16:
+        raise ValueError("grouped_gemm_tn: operands must be 16-B aligned")
+    if out is not None:
+        if out.dtype != torch.float32:
+            raise TypeError("grouped_gemm_tn output must be fp32")
+        if out.shape != (G, N, K) or out.stride(2) != 1 or out.device != x.device:
+            raise ValueError("grouped_gemm_tn output must be fp32 [G, N, K] with unit inner stride on x's device")
+        if out.data_ptr() % 16 or out.stride(1) % 4 or out.stride(0) % 4:
+            raise ValueError("grouped_gemm_tn output rows and expert blocks must be 16-B aligned")
+    return int(cap), int(G), int(N), int(K)
+
+
+def grouped_gemm_tn(dy: torch.Tensor, x: torch.Tensor, counts: torch.Tensor, out: Optional[torch.Tensor] = None,
+                    alpha: float = 1.0) -> torch.Tensor:
+    """Weight gradients of ``grouped_gemm_nt``: ``out[g] = alpha * dy[rows of g].T @ x[rows of g]``,
+    fp32 ``[G, N, K]`` (dy [cap, N], x [cap, K] bf16, same row rules).  Both operands are read
+    row-major through ds_read_b64_tr_b16; rows outside an expert are masked at the load (they
+    may hold anything, NaN included); an expert with no rows gets zeros.  One workgroup per
+    (expert, 128 x 128 tile) walks the expert's rows in order: deterministic, no atomics."""
+    cap, G, N, K = grouped_tn_validate(dy, x, counts, out)
     if out is None:
         out = torch.empty((G, N, K), dtype=torch.float32, device=x.device)
-    if out.dtype != torch.float32 or out.shape != (G, N, K) or out.stride(2) != 1 or out.device != x.device:
-        raise ValueError("grouped_gemm_tn output must be fp32 [G, N, K] with unit inner stride")
     _D().grouped_gemm_tn(dy.data_ptr(), x.data_ptr(), out.data_ptr(), counts.data_ptr(), cap, N, K, G,
                          dy.stride(0) if cap > 1 else N, x.stride(0) if cap > 1 else K, out.stride(1), out.stride(0),
                          float(alpha), counts.dtype == torch.int64, _stream(x))
@@ -542,14 +560,11 @@ def grouped_gemm_nn(dy: torch.Tensor, w: torch.Tensor, counts: torch.Tensor, out
     return out
 
 
-def grouped_gemm_nt_swiglu(x: torch.Tensor, w: torch.Tensor, counts: torch.Tensor, h: Optional[torch.Tensor] = None,
-                           glu: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
-                           alpha: float = 1.0):
-    """``grouped_gemm_nt`` of an interleaved gate|up weight with the SwiGLU gate in its
-    epilogue: returns ``(h, glu)``, ``h`` [cap, N] bf16 exactly what ``grouped_gemm_nt(x, w,
-    counts, bias=bias, alpha=alpha)`` writes and ``glu[r, j] = silu(h[r, 2j]) * h[r, 2j + 1]``
-    ([cap, N / 2] bf16, bit for bit ``swiglu_pairs(h)``), written by the same kernel for the
-    same rows.  Rows at or past ``sum(counts)`` of both outputs are left untouched."""
+def grouped_swiglu_validate(x, w, counts, h=None, glu=None, bias=None):
+    """Argument rules of ``grouped_gemm_nt_swiglu`` that need no GPU: ``grouped_validate``'s for
+    ``x``, ``w``, ``counts``, ``bias`` and a bf16 ``h``, and for ``glu`` bf16 ``[cap, N / 2]`` with
+    unit column stride, an 8-B aligned start and a row stride that is a multiple of 4 elements
+    and at least ``N / 2``.  Returns ``(cap, G, N, K)``."""
     cap, G, N, K = grouped_validate(x, w, counts, h, bias, torch.bfloat16)
     if h is not None and h.dtype != torch.bfloat16:
         raise TypeError("grouped_gemm_nt_swiglu: h must be bf16")
@@ -560,6 +575,20 @@ def grouped_gemm_nt_swiglu(x: torch.Tensor, w: torch.Tensor, counts: torch.Tenso
             raise ValueError("grouped_gemm_nt_swiglu: glu must be [cap, N / 2] with unit column stride on x's device")
         if glu.data_ptr() % 8 or (cap > 1 and glu.stride(0) % 4):
             raise ValueError("grouped_gemm_nt_swiglu: glu rows must be 8-B aligned")
+        if cap > 1 and glu.stride(0) < N // 2:
+            raise ValueError("grouped_gemm_nt_swiglu: the rows of glu must not overlap (row stride >= N / 2)")
+    return cap, G, N, K
+
+
+def grouped_gemm_nt_swiglu(x: torch.Tensor, w: torch.Tensor, counts: torch.Tensor, h: Optional[torch.Tensor] = None,
+                           glu: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
+                           alpha: float = 1.0):
+    """``grouped_gemm_nt`` of an interleaved gate|up weight with the SwiGLU gate in its
+    epilogue: returns ``(h, glu)``, ``h`` [cap, N] bf16 exactly what ``grouped_gemm_nt(x, w,
+    counts, bias=bias, alpha=alpha)`` writes and ``glu[r, j] = silu(h[r, 2j]) * h[r, 2j + 1]``
+    ([cap, N / 2] bf16, bit for bit ``swiglu_pairs(h)``), written by the same kernel for the
+    same rows.  Rows at or past ``sum(counts)`` of both outputs are left untouched."""
+    cap, G, N, K = grouped_swiglu_validate(x, w, counts, h, glu, bias)
     if h is None:
         h = torch.empty((cap, N), dtype=torch.bfloat16, device=x.device)
     if glu is None:

@@ -1,4 +1,5 @@
-"""The data recipe of tests/test_gpu_gemm_views.py, checked from the inputs alone (no GPU).
+"""The data recipe of tests/test_gpu_gemm_views.py and tests/test_gpu_grouped_views.py, checked
+from the inputs alone (no GPU).
 
 Those tests compare every GEMM route bitwise with an fp64 reference.  That is only sound
 if the fp32 result is exact whatever the summation order, and it only bites if the bf16
@@ -10,7 +11,14 @@ every (K, R) the GPU module uses; they measure nothing of the kernels.
 import pytest
 import torch
 
-from test_gpu_gemm_views import RECIPE_KR, SWIGLU_R, _framed, _int_values, _ints, _out_frame, _rmax, SENTINEL
+import test_gpu_gemm_views
+import test_gpu_grouped_views
+from test_gpu_gemm_views import SWIGLU_R, _framed, _int_values, _ints, _out_frame, _rmax, SENTINEL
+
+# every (K, R) of both modules whose output is rounded to bf16; the grouped weight gradient's
+# reduction lengths (the experts' row counts) have fp32 outputs only
+RECIPE_KR = sorted(set(test_gpu_gemm_views.RECIPE_KR) | set(test_gpu_grouped_views.RECIPE_KR))
+RECIPE_FP32_ONLY = sorted(set(test_gpu_grouped_views.RECIPE_TN_RED) - set(RECIPE_KR))
 
 M, N = 96, 80
 
@@ -25,6 +33,11 @@ def test_recipe_covers_the_issue_lengths():
     assert {8, 72, 200, 64, 192, 256, 96, 128, 384, 320, 7, 1000} <= ks
     assert all(R == (SWIGLU_R if R < 64 else 64) for _, R in RECIPE_KR)
     assert all(K * R * R <= 2 ** 23 for K, R in RECIPE_KR)
+    assert set(test_gpu_gemm_views.RECIPE_KR) <= set(RECIPE_KR)
+    # the grouped module: the register-loop gate, and the experts' row counts as reduction lengths
+    assert {(72, SWIGLU_R), (136, SWIGLU_R), (136, 64)} <= set(RECIPE_KR)
+    assert {1, 7, 50, 70, 127, 129, 320} <= {k for k, _ in test_gpu_grouped_views.RECIPE_TN_RED}
+    assert all(R == 64 and K * R * R <= 2 ** 23 for K, R in test_gpu_grouped_views.RECIPE_TN_RED)
 
 
 @pytest.mark.parametrize("K,R", RECIPE_KR)
@@ -39,7 +52,7 @@ def test_operands_survive_bf16(K, R):
     assert int(iv.min()) == -R and int(iv.max()) == R                # the whole range is used
 
 
-@pytest.mark.parametrize("K,R", RECIPE_KR)
+@pytest.mark.parametrize("K,R", RECIPE_KR + RECIPE_FP32_ONLY)
 def test_fp32_product_is_exact_in_any_order(K, R):
     a, b = _operands(K, R)
     exact = a.double() @ b.double().T
