@@ -13,6 +13,7 @@ void register_swiglu_ops(pybind11::module_& m);
 void register_grouped_gemm_ops(pybind11::module_& m);
 void register_moe_gate_ops(pybind11::module_& m);
 void register_moe_router_ops(pybind11::module_& m);
+void register_flash_attn_ops(pybind11::module_& m);
 
 void register_ops(pybind11::module_& m) {
   register_layout_ops(m);
@@ -24,6 +25,7 @@ void register_ops(pybind11::module_& m) {
   register_grouped_gemm_ops(m);
   register_moe_gate_ops(m);
   register_moe_router_ops(m);
+  register_flash_attn_ops(m);
 }
 
 }  // namespace dev

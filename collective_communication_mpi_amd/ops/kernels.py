@@ -972,3 +972,164 @@ def moe_router_logits(x: torch.Tensor, router: torch.Tensor) -> torch.Tensor:
     (``moe_router_logits_backward``), and gradients are computed only for the inputs that ask."""
     moe_router_logits_validate(x, router)
     return _MoERouterLogits.apply(x, router)
+
+
+# ---------------------------------------------------------------------------
+# flash attention (csrc/device/flash_attn.hip)
+# ---------------------------------------------------------------------------
+FLASH_BQ = 128  # query rows per workgroup of the forward / dQ kernels (csrc/device/flash_attn.hpp kFlashBQ)
+FLASH_BK = 64   # keys per step of their key loop = keys per workgroup of the dK/dV kernel (kFlashBK)
+FLASH_HEAD_DIMS = (64, 128)
+_FLASH_MAX_GRID = 65535  # B and Hq are grid dimensions
+
+
+def _flash_view_check(name: str, t) -> None:
+    """The stride rules of a [B, S, H, D] operand read as a view: unit stride on D, every other
+    stride (of an axis longer than 1) a multiple of 8 elements, 16-byte-aligned base."""
+    if t.stride(3) != 1:
+        raise ValueError(f"flash_attention: {name} must have unit stride on the head dim, got strides {t.stride()}")
+    for ax in range(3):
+        if t.shape[ax] > 1 and t.stride(ax) % 8:
+            raise ValueError(f"flash_attention: stride {t.stride(ax)} of axis {ax} of {name} is not a multiple of 8 "
+                             "elements")
+    if t.data_ptr() % 16:
+        raise ValueError(f"flash_attention: {name} must start at a 16-byte-aligned address")
+
+
+def _flash_strides(t):
+    return tuple(t.stride(ax) if t.shape[ax] > 1 else 0 for ax in range(3))
+
+
+def flash_attention_validate(q, k, v):
+    """Argument rules of ``flash_attention`` that need no GPU; raises TypeError (dtypes) /
+    ValueError (shapes, strides, alignment) and returns ``(B, S, Hq, Hkv, D)``.  ``q`` is
+    [B, S, Hq, D], ``k`` and ``v`` [B, S, Hkv, D], all bf16, taken as views: unit stride on D,
+    batch / sequence / head strides multiples of 8 elements, 16-byte-aligned base.
+    ``Hq % Hkv == 0``, ``D`` in {64, 128}, ``S >= 1``."""
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if t.dtype != torch.bfloat16:
+            raise TypeError(f"flash_attention expects bf16 {name}, got {t.dtype}")
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if t.dim() != 4:
+            raise ValueError(f"flash_attention: {name} must be [B, S, H, D], got {tuple(t.shape)}")
+    B, S, Hq, D = q.shape
+    Hkv = k.shape[2]
+    if tuple(k.shape) != (B, S, Hkv, D) or tuple(v.shape) != (B, S, Hkv, D):
+        raise ValueError(f"flash_attention: k and v must be [B = {B}, S = {S}, Hkv, D = {D}] like q, got "
+                         f"{tuple(k.shape)} and {tuple(v.shape)}")
+    if D not in FLASH_HEAD_DIMS:
+        raise ValueError(f"flash_attention: the head dim must be one of {FLASH_HEAD_DIMS}, got {D}")
+    if S < 1:
+        raise ValueError("flash_attention: the sequence must have at least one position")
+    if S > 1 << 30:
+        raise ValueError("flash_attention: S must be at most 2^30")
+    if Hkv < 1 or Hq % Hkv:
+        raise ValueError(f"flash_attention: Hq = {Hq} must be a multiple of Hkv = {Hkv}")
+    if not (1 <= B <= _FLASH_MAX_GRID and Hq <= _FLASH_MAX_GRID):
+        raise ValueError(f"flash_attention: B and Hq must be in [1, {_FLASH_MAX_GRID}], got {B} and {Hq}")
+    if k.device != q.device or v.device != q.device:
+        raise ValueError("flash_attention: q, k and v must be on one device")
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        _flash_view_check(name, t)
+    return int(B), int(S), int(Hq), int(Hkv), int(D)
+
+
+def _flash_result(name: str, t, shape, dtype, like):
+    """A caller's output / workspace: the exact shape, dtype and device, contiguous, aligned."""
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=like.device)
+    if t.dtype != dtype:
+        raise TypeError(f"flash_attention: {name} must be {dtype}, got {t.dtype}")
+    if tuple(t.shape) != tuple(shape) or not t.is_contiguous() or t.device != like.device:
+        raise ValueError(f"flash_attention: {name} must be a contiguous {tuple(shape)} tensor on {like.device}")
+    if t.data_ptr() % 16:
+        raise ValueError(f"flash_attention: {name} must start at a 16-byte-aligned address")
+    return t
+
+
+def _flash_scale(scale, D: int) -> float:
+    s = D ** -0.5 if scale is None else float(scale)
+    if not (s == s and abs(s) != float("inf")):
+        raise ValueError("flash_attention: scale must be finite")
+    return s
+
+
+def flash_attention_forward(q, k, v, causal: bool = True, scale: Optional[float] = None, out=None, lse=None):
+    """``softmax(scale * q k^T [+ causal mask]) v`` per (batch, query head), GQA without expanding
+    K or V (``k_flash_fwd``): returns ``(out [B, S, Hq, D] bf16 contiguous, lse [B, Hq, S] fp32)``,
+    ``lse`` the natural log of each row's sum of ``exp(scale * score)``.  Operands as
+    ``flash_attention_validate`` describes (views: no transposed copy); ``scale`` defaults to
+    ``1 / sqrt(D)``.  Plain tensors, no autograd; no host synchronisation, and no allocation
+    when ``out`` and ``lse`` are passed, so the call can be captured in a graph."""
+    B, S, Hq, Hkv, D = flash_attention_validate(q, k, v)
+    sc = _flash_scale(scale, D)
+    out = _flash_result("out", out, (B, S, Hq, D), torch.bfloat16, q)
+    lse = _flash_result("lse", lse, (B, Hq, S), torch.float32, q)
+    _D().flash_attn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr(),
+                        *_flash_strides(q), *_flash_strides(k), *_flash_strides(v), B, S, Hq, Hkv, D, bool(causal), sc,
+                        _stream(q))
+    return out, lse
+
+
+def flash_attention_backward(dout, q, k, v, out, lse, causal: bool = True, scale: Optional[float] = None,
+                             dq=None, dk=None, dv=None, delta=None):
+    """``(dq, dk, dv)`` of ``flash_attention_forward``: P is recomputed from ``q``, ``k`` and
+    ``lse``; ``delta = rowsum(dout * out)`` is taken from the stored bf16 ``out`` (``delta``
+    [B, Hq, S] fp32 is its workspace).  ``dout`` follows the stride rules of ``q``; ``dq`` is
+    bf16 contiguous in the layout of ``out``, ``dk`` and ``dv`` bf16 contiguous [B, S, Hkv, D].
+    Three launches (delta, dK/dV, dQ): one workgroup owns each dK/dV key block and sums over its
+    query heads and query blocks in a fixed order, one owns each dQ block, so there are no
+    atomics and the gradients are bitwise reproducible."""
+    B, S, Hq, Hkv, D = flash_attention_validate(q, k, v)
+    sc = _flash_scale(scale, D)
+    if dout.dtype != torch.bfloat16:
+        raise TypeError(f"flash_attention expects bf16 dout, got {dout.dtype}")
+    if tuple(dout.shape) != (B, S, Hq, D) or dout.device != q.device:
+        raise ValueError(f"flash_attention: dout must be {(B, S, Hq, D)} on {q.device}, got {tuple(dout.shape)}")
+    _flash_view_check("dout", dout)
+    if out is None or lse is None:
+        raise ValueError("flash_attention_backward needs the forward's out and lse")
+    out = _flash_result("out", out, (B, S, Hq, D), torch.bfloat16, q)
+    lse = _flash_result("lse", lse, (B, Hq, S), torch.float32, q)
+    dq = _flash_result("dq", dq, (B, S, Hq, D), torch.bfloat16, q)
+    dk = _flash_result("dk", dk, (B, S, Hkv, D), torch.bfloat16, q)
+    dv = _flash_result("dv", dv, (B, S, Hkv, D), torch.bfloat16, q)
+    delta = _flash_result("delta", delta, (B, Hq, S), torch.float32, q)
+    _D().flash_attn_bwd(dout.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr(),
+                        delta.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), *_flash_strides(dout),
+                        *_flash_strides(q), *_flash_strides(k), *_flash_strides(v), B, S, Hq, Hkv, D, bool(causal), sc,
+                        _stream(q))
+    return dq, dk, dv
+
+
+def _flash_is_view(t) -> bool:
+    return (t.stride(3) == 1 and all(t.shape[ax] == 1 or t.stride(ax) % 8 == 0 for ax in range(3))
+            and t.data_ptr() % 16 == 0)
+
+
+class _FlashAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, causal, scale):
+        out, lse = flash_attention_forward(q, k, v, causal, scale)
+        ctx.save_for_backward(q, k, v, out, lse)
+        ctx.causal, ctx.scale = causal, scale
+        ctx.mark_non_differentiable(lse)
+        return out, lse
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout, _dlse):
+        q, k, v, out, lse = ctx.saved_tensors
+        if not _flash_is_view(dout):  # e.g. an expanded or transposed gradient
+            dout = dout.contiguous()
+        dq, dk, dv = flash_attention_backward(dout, q, k, v, out, lse, ctx.causal, ctx.scale)
+        return dq, dk, dv, None, None
+
+
+def flash_attention(q, k, v, causal: bool = True, scale: Optional[float] = None):
+    """Differentiable ``flash_attention_forward``: ``out`` [B, S, Hq, D] bf16 of the bf16 views
+    ``q`` [B, S, Hq, D], ``k`` / ``v`` [B, S, Hkv, D] (GQA: query head h reads kv head
+    ``h // (Hq / Hkv)``), differentiable in all three.  Autograd keeps ``q``, ``k``, ``v``,
+    ``out`` and ``lse``; nothing of size S x S exists."""
+    flash_attention_validate(q, k, v)
+    return _FlashAttention.apply(q, k, v, bool(causal), scale)[0]

@@ -13,9 +13,13 @@ post-accumulate hook -- on the communication stream, and ``finish()`` joins it.
 
 The reference's DP is sharding plus ``dp_comm`` (data/data_parallel_preprocess.py:45-59,
 model/func_impl.py:61-62, README.md:177); this is the gradient synchronisation the north
-star adds on that communicator.  Attention is PyTorch's SDPA (the model compute around
-the collective, not a framework kernel); RoPE is left out (no effect on gradient sizes
-or the GEMM work).  Random-init weights, synthetic token ids.
+star adds on that communicator.  Attention is chosen by ``LlamaConfig.attention``: "sdpa"
+(the default) is PyTorch's SDPA on transposed q/k/v with the kv heads expanded by
+``repeat_interleave``; "flash" is the project's own kernel (``ops.flash_attention``,
+csrc/device/flash_attn.hip), which reads the projections' [B, S, H, hd] views as they are,
+never expands K or V and writes the [B * S, d] input of ``wo`` directly (head dim 64 or 128).
+RoPE is left out (no effect on gradient sizes or the GEMM work).  Random-init weights,
+synthetic token ids.
 """
 from __future__ import annotations
 
@@ -26,6 +30,7 @@ from typing import Dict, List, Optional
 import torch
 import torch.nn.functional as F
 
+from ..ops.kernels import FLASH_HEAD_DIMS, flash_attention
 from .ddp import DistributedDataParallel
 from .tensor_parallel import ColumnParallelLinear, ParallelSwiGLUMLP, RowParallelLinear
 
@@ -39,6 +44,7 @@ class LlamaConfig:
     vocab: int = 128256
     layers: int = 32
     eps: float = 1e-5
+    attention: str = "sdpa"  # "sdpa" (PyTorch) or "flash" (ops.flash_attention, head dim 64 / 128)
 
     @property
     def head_dim(self) -> int:
@@ -51,6 +57,7 @@ class LlamaConfig:
 
 
 LLAMA3_8B = LlamaConfig()
+ATTENTION_KINDS = ("sdpa", "flash")
 
 
 class RMSNorm(torch.nn.Module):
@@ -68,6 +75,10 @@ class LlamaBlock(torch.nn.Module):
         super().__init__()
         d, kv = cfg.d, cfg.kv_heads * cfg.head_dim
         self.cfg = cfg
+        if cfg.attention not in ATTENTION_KINDS:
+            raise ValueError(f"LlamaConfig.attention must be one of {ATTENTION_KINDS}, got {cfg.attention!r}")
+        if cfg.attention == "flash" and cfg.head_dim not in FLASH_HEAD_DIMS:
+            raise ValueError(f'attention="flash" needs a head dim in {FLASH_HEAD_DIMS}, got {cfg.head_dim}')
         kw = dict(bias=False, device=device, dtype=dtype, init="device")
         self.attn_norm = RMSNorm(d, cfg.eps, device, dtype)
         self.wq = ColumnParallelLinear(d, d, tp, seed=seed, **kw)
@@ -81,6 +92,11 @@ class LlamaBlock(torch.nn.Module):
         cfg = self.cfg
         hd = cfg.head_dim
         n = self.attn_norm(x)
+        if cfg.attention == "flash":  # the projections' views as they are; K and V stay at kv_heads
+            o = flash_attention(self.wq(n).view(batch, seq, cfg.heads, hd), self.wk(n).view(batch, seq, cfg.kv_heads, hd),
+                                self.wv(n).view(batch, seq, cfg.kv_heads, hd), causal=True)
+            h = x + self.wo(o.view(batch * seq, cfg.d))
+            return h + self.mlp(self.mlp_norm(h))
         q = self.wq(n).view(batch, seq, cfg.heads, hd).transpose(1, 2)
         k = self.wk(n).view(batch, seq, cfg.kv_heads, hd).transpose(1, 2)
         v = self.wv(n).view(batch, seq, cfg.kv_heads, hd).transpose(1, 2)
