@@ -31,6 +31,23 @@
 //                    dS = P (dP - delta), dV^T += dO^T P, dK^T += Q^T dS.
 //   k_flash_bwd_dq   workgroup = kFlashBQ query rows of one (batch, query head); per key step
 //                    S^T, dP^T with the query on the lane, dQ^T += K^T dS^T.
+// Chunk form (ops.flash_attention_chunk, the kernels of parallel/context_parallel.py): the same four
+// kernels with separate lengths Sq (rows of q, dout, out, dq, lse, delta) and Sk (rows of k, v, dk,
+// dv) and the position q_pos0 >= 0 of query row 0; causal: key j is visible to row i iff
+// j <= q_pos0 + i, so key 0 is visible to every row and no row is ever fully masked.  Every skip
+// rule moves with the offset: the forward / dQ key loop ends at min(Sk, q_pos0 + q0 + kFlashBQ), a
+// wave skips steps above q_pos0 + its last row, the dK/dV kernel starts at query step
+// max(0, key0 - q_pos0) / kFlashBwdQ, and a key block no query of the chunk sees has zero steps and
+// stores exact zeros (a reduce-scatter sums it).  A row's sums run over the same key steps in the
+// same order whichever chunk holds it and a wholly masked step is an exact no-op (alpha = 1,
+// p = 0), so out, lse and dq of a chunk are bitwise the full call's rows.  SEG: the key axis of
+// k / v / dk / dv is cut into segments of L keys (Sk % L == 0), key j at (j / L) * seg + (j % L) * s,
+// each tensor with strides of its own: [n, B, L, Hkv, D], the layout an all-gather of per-rank
+// shards produces.  The map is applied per key row in every fetch and store, so a tile may
+// straddle segments; keys >= Sk and whatever lies between segments are never touched.  Self-attention
+// is the kSelf instantiation of the same kernels, where Sq = Sk and q_pos0 = 0 are compile-time facts:
+// the code, the speed and the bits it always had.
+//
 // P is recomputed in both backward kernels (seven products per tile pair instead of five): no
 // atomics, no hand-off between workgroups, every sum has one owner and a fixed order, so all
 // five outputs are bitwise reproducible.  Only plain vector stores write global memory.
@@ -65,8 +82,11 @@ struct FwdArgs {
   uint16_t* out;
   float* lse;
   Strides sq, sk, sv;
-  int S, Hq, Hkv;
+  int Sq, Hq, Hkv;
   float scale_log2;
+  // the chunk form's own arguments follow those of self-attention, whose layout is unchanged
+  int Sk, q_pos0, L;
+  int64_t kseg, vseg;  // segment strides of k / v (kSegmented only)
 };
 
 struct BwdArgs {
@@ -74,9 +94,29 @@ struct BwdArgs {
   const float *lse, *delta;
   uint16_t *dq, *dk, *dv;
   Strides sq, sk, sv, sdo;
-  int S, Hq, Hkv;
+  int Sq, Hq, Hkv;
   float scale, scale_log2;
+  // the chunk form's own arguments follow those of self-attention, whose layout is unchanged
+  int Sk, q_pos0, L;
+  Strides sdk, sdv;
+  int64_t kseg, vseg, dkseg, dvseg;  // segment strides of k / v / dk / dv (kSegmented only)
 };
+
+// Instantiations of every kernel.  kSelf is self-attention as it always was: one length (Sk = Sq),
+// q_pos0 = 0 and contiguous dk / dv are compile-time facts there, so it keeps its code and its
+// speed; kChunk reads Sq, Sk and q_pos0 from the arguments and writes dk / dv through their
+// strides; kSegmented adds the segmented key axis.
+constexpr int kSelf = 0, kChunk = 1, kSegmented = 2;
+
+// Element offset of key row `key` on the key axis of k / v / dk / dv.  SEG: the axis is cut into
+// segments of L keys, `seg` elements apart (the rank-major layout of an all-gather); otherwise
+// one run of stride s.  Applied per key row, so a tile may straddle segments.
+template <bool SEG>
+__device__ __forceinline__ int64_t key_off(int key, int L, int64_t seg, int64_t s) {
+  if (!SEG) return (int64_t)key * s;
+  const int n = key / L;
+  return (int64_t)n * seg + (int64_t)(key - n * L) * s;
+}
 
 __device__ __forceinline__ f4 mma32(bf16x8 a, bf16x8 b, f4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
@@ -107,7 +147,7 @@ __device__ __forceinline__ void st_g8(uint16_t* p, f4 v, float mul) {
   *reinterpret_cast<uint2*>(p) = uint2{pk_bf16(v[0] * mul, v[1] * mul), pk_bf16(v[2] * mul, v[3] * mul)};
 }
 
-template <int D, bool CAUSAL>
+template <int D, bool CAUSAL, int MODE>
 __global__ __launch_bounds__(kFlashThreads) void k_flash_fwd(const FwdArgs a) {
   constexpr int LDK = D + 8, LDT = kFlashBK + 8, KK = D / 32, DT = D / 16;
   constexpr int KP = kFlashBK * (D / 8) / kFlashThreads, VP = D / 32;
@@ -115,7 +155,8 @@ __global__ __launch_bounds__(kFlashThreads) void k_flash_fwd(const FwdArgs a) {
   __shared__ __attribute__((aligned(16))) uint16_t Vt[D * LDT];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c = lane & 15, g = lane >> 4;
   const int qb = (int)(gridDim.x - 1 - blockIdx.x), h = blockIdx.y, b = blockIdx.z;  // heaviest blocks first
-  const int hk = h / (a.Hq / a.Hkv), S = a.S;
+  constexpr bool SEG = MODE == kSegmented;
+  const int hk = h / (a.Hq / a.Hkv), Sq = a.Sq, Sk = MODE ? a.Sk : Sq, p0 = MODE ? a.q_pos0 : 0;  // query row i sits at position p0 + i
   const int q0 = qb * kFlashBQ, qw = q0 + wave * (16 * kFlashQT);
   const uint16_t* qp = a.q + b * a.sq.b + h * a.sq.h;
   const uint16_t* kp = a.k + b * a.sk.b + hk * a.sk.h;
@@ -126,7 +167,7 @@ __global__ __launch_bounds__(kFlashThreads) void k_flash_fwd(const FwdArgs a) {
   for (int t = 0; t < kFlashQT; ++t) {
     const int qi = qw + 16 * t + c;
 #pragma unroll
-    for (int kk = 0; kk < KK; ++kk) qf[t][kk] = as_frag(ld_g16(qp + (int64_t)qi * a.sq.s + 32 * kk + 8 * g, qi < S));
+    for (int kk = 0; kk < KK; ++kk) qf[t][kk] = as_frag(ld_g16(qp + (int64_t)qi * a.sq.s + 32 * kk + 8 * g, qi < Sq));
   }
   f4 o[kFlashQT][DT];
   float m[kFlashQT], l[kFlashQT];
@@ -138,19 +179,19 @@ __global__ __launch_bounds__(kFlashThreads) void k_flash_fwd(const FwdArgs a) {
     for (int dt = 0; dt < DT; ++dt) o[t][dt] = f4{0.f, 0.f, 0.f, 0.f};
   }
 
-  const int kend = CAUSAL ? min(S, q0 + kFlashBQ) : S;
+  const int kend = CAUSAL ? min(Sk, p0 + q0 + kFlashBQ) : Sk;
   const int nt = (kend + kFlashBK - 1) / kFlashBK;
   uint4 kr[KP], vr[VP];
   auto fetch = [&](int key0) {
 #pragma unroll
     for (int i = 0; i < KP; ++i) {
       const int p = tid + kFlashThreads * i, key = key0 + p / (D / 8);
-      kr[i] = ld_g16(kp + (int64_t)key * a.sk.s + (p % (D / 8)) * 8, key < S);
+      kr[i] = ld_g16(kp + key_off<SEG>(key, a.L, a.kseg, a.sk.s) + (p % (D / 8)) * 8, key < Sk);
     }
 #pragma unroll
     for (int i = 0; i < VP; ++i) {
       const int key = key0 + lane;
-      vr[i] = ld_g16(vp + (int64_t)key * a.sv.s + (wave + 4 * i) * 8, key < S);
+      vr[i] = ld_g16(vp + key_off<SEG>(key, a.L, a.vseg, a.sv.s) + (wave + 4 * i) * 8, key < Sk);
     }
   };
   fetch(0);
@@ -166,7 +207,7 @@ __global__ __launch_bounds__(kFlashThreads) void k_flash_fwd(const FwdArgs a) {
     for (int i = 0; i < VP; ++i) st_transposed(Vt, LDT, (wave + 4 * i) * 8, perm64(lane), vr[i]);
     __syncthreads();
     if (it + 1 < nt) fetch(key0 + kFlashBK);
-    if (CAUSAL && key0 > qw + 16 * kFlashQT - 1) continue;  // every key above every row of this wave
+    if (CAUSAL && key0 > p0 + qw + 16 * kFlashQT - 1) continue;  // every key above every row of this wave
 
     f4 s[4][kFlashQT];  // s[kt][t][r] = score of key key0 + 16 kt + 4g + r, query qw + 16 t + c
 #pragma unroll
@@ -182,7 +223,7 @@ __global__ __launch_bounds__(kFlashThreads) void k_flash_fwd(const FwdArgs a) {
         s[kt][t] = acc;
       }
     }
-    const bool edge = key0 + kFlashBK > S || (CAUSAL && key0 + kFlashBK - 1 > qw);
+    const bool edge = key0 + kFlashBK > Sk || (CAUSAL && key0 + kFlashBK - 1 > p0 + qw);
 #pragma unroll
     for (int t = 0; t < kFlashQT; ++t) {
       const int qi = qw + 16 * t + c;
@@ -194,14 +235,15 @@ __global__ __launch_bounds__(kFlashThreads) void k_flash_fwd(const FwdArgs a) {
           float x = s[kt][t][r] * a.scale_log2;
           if (edge) {
             const int key = key0 + 16 * kt + 4 * g + r;
-            if (key >= S || (CAUSAL && key > qi)) x = -INFINITY;
+            if (key >= Sk || (CAUSAL && key > p0 + qi)) x = -INFINITY;
           }
           s[kt][t][r] = x;
           mx = fmaxf(mx, x);
         }
       mx = fmaxf(mx, __shfl_xor(mx, 16));
       mx = fmaxf(mx, __shfl_xor(mx, 32));
-      // key 0 is visible to every row and step 0 is never skipped, so mn is finite from step 0 on
+      // key 0 is visible to every row (p0 >= 0) and step 0 is never skipped, so mn is finite from step 0
+      // on; a later step that is wholly masked for a row is an exact no-op (alpha = 1, p = 0)
       const float mn = fmaxf(m[t], mx);
       const float alpha = fast_exp2(m[t] - mn);
       m[t] = mn;
@@ -236,12 +278,12 @@ __global__ __launch_bounds__(kFlashThreads) void k_flash_fwd(const FwdArgs a) {
     const int qi = qw + 16 * t + c;
     float lt = l[t] + __shfl_xor(l[t], 16);
     lt += __shfl_xor(lt, 32);
-    if (qi >= S) continue;
+    if (qi >= Sq) continue;
     const float inv = 1.0f / lt;
-    uint16_t* op = a.out + (((int64_t)b * S + qi) * a.Hq + h) * D + 4 * g;
+    uint16_t* op = a.out + (((int64_t)b * Sq + qi) * a.Hq + h) * D + 4 * g;
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) st_g8(op + 16 * dt, o[t][dt], inv);
-    if (g == 0) a.lse[((int64_t)b * a.Hq + h) * S + qi] = (m[t] + __log2f(lt)) * kLn2;
+    if (g == 0) a.lse[((int64_t)b * a.Hq + h) * Sq + qi] = (m[t] + __log2f(lt)) * kLn2;
   }
 }
 
@@ -269,7 +311,7 @@ __global__ __launch_bounds__(kFlashThreads) void k_flash_delta(const uint16_t* d
   if (ok && (c >> 2) == g) delta[(b * Hq + h) * S + s] = d;
 }
 
-template <int D, bool CAUSAL>
+template <int D, bool CAUSAL, int MODE>
 __global__ __launch_bounds__(kFlashThreads) void k_flash_bwd_dkv(const BwdArgs a) {
   constexpr int LDK = D + 8, LDQ = kFlashBwdQ + 8, KK = D / 32, DT = D / 16, NP = D / 64;
   __shared__ __attribute__((aligned(16))) uint16_t Qs[kFlashBwdQ * LDK];
@@ -280,29 +322,32 @@ __global__ __launch_bounds__(kFlashThreads) void k_flash_bwd_dkv(const BwdArgs a
   __shared__ __attribute__((aligned(16))) float Ds[kFlashBwdQ];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c = lane & 15, g = lane >> 4;
   const int kb = blockIdx.x, hk = blockIdx.y, b = blockIdx.z;
-  const int S = a.S, rep = a.Hq / a.Hkv;
+  constexpr bool SEG = MODE == kSegmented;
+  const int Sq = a.Sq, Sk = MODE ? a.Sk : Sq, p0 = MODE ? a.q_pos0 : 0, rep = a.Hq / a.Hkv;
   const int key0 = kb * kFlashBK, kw = key0 + 16 * wave, keyi = kw + c;
-  const uint16_t* kp = a.k + b * a.sk.b + hk * a.sk.h + (int64_t)keyi * a.sk.s;
-  const uint16_t* vp = a.v + b * a.sv.b + hk * a.sv.h + (int64_t)keyi * a.sv.s;
+  const uint16_t* kp = a.k + b * a.sk.b + hk * a.sk.h + key_off<SEG>(keyi, a.L, a.kseg, a.sk.s);
+  const uint16_t* vp = a.v + b * a.sv.b + hk * a.sv.h + key_off<SEG>(keyi, a.L, a.vseg, a.sv.s);
   bf16x8 kf[KK], vf[KK];
 #pragma unroll
   for (int kk = 0; kk < KK; ++kk) {
-    kf[kk] = as_frag(ld_g16(kp + 32 * kk + 8 * g, keyi < S));
-    vf[kk] = as_frag(ld_g16(vp + 32 * kk + 8 * g, keyi < S));
+    kf[kk] = as_frag(ld_g16(kp + 32 * kk + 8 * g, keyi < Sk));
+    vf[kk] = as_frag(ld_g16(vp + 32 * kk + 8 * g, keyi < Sk));
   }
   f4 dk[DT], dv[DT];
 #pragma unroll
   for (int dt = 0; dt < DT; ++dt) dk[dt] = dv[dt] = f4{0.f, 0.f, 0.f, 0.f};
 
-  const int qs0 = CAUSAL ? key0 / kFlashBwdQ : 0;  // query steps wholly before the key block see none of it
-  const int nq = (S + kFlashBwdQ - 1) / kFlashBwdQ - qs0;
+  // query steps wholly before the key block see none of it; a key block past every query of the
+  // chunk has no step at all and stores exact zeros
+  const int qs0 = CAUSAL ? (MODE ? max(0, key0 - p0) : key0) / kFlashBwdQ : 0;
+  const int nqs = (Sq + kFlashBwdQ - 1) / kFlashBwdQ - qs0, nq = MODE ? max(0, nqs) : nqs;
   const int steps = rep * nq;  // query heads in order, query steps in order inside each
   const int row = tid & 31, cb = tid >> 5;
   uint4 qr[NP], dr[NP];
   float lv = 0.f, dl = 0.f;
   auto fetch = [&](int i) {
     const int h = hk * rep + i / nq, qi = (qs0 + i % nq) * kFlashBwdQ + row;
-    const bool ok = qi < S;
+    const bool ok = qi < Sq;
     const uint16_t* qp = a.q + b * a.sq.b + h * a.sq.h + (int64_t)qi * a.sq.s;
     const uint16_t* dp = a.dout + b * a.sdo.b + h * a.sdo.h + (int64_t)qi * a.sdo.s;
 #pragma unroll
@@ -311,7 +356,7 @@ __global__ __launch_bounds__(kFlashThreads) void k_flash_bwd_dkv(const BwdArgs a
       dr[j] = ld_g16(dp + (cb + 8 * j) * 8, ok);
     }
     if (tid < kFlashBwdQ) {
-      const int64_t o = ((int64_t)b * a.Hq + h) * S + qi;
+      const int64_t o = ((int64_t)b * a.Hq + h) * Sq + qi;
       lv = ok ? a.lse[o] * kLog2e : 0.f;
       dl = ok ? a.delta[o] : 0.f;
     }
@@ -334,7 +379,7 @@ __global__ __launch_bounds__(kFlashThreads) void k_flash_bwd_dkv(const BwdArgs a
     }
     __syncthreads();
     if (i + 1 < steps) fetch(i + 1);
-    if (CAUSAL && qbase + kFlashBwdQ - 1 < kw) continue;  // every query of the step before every key of this wave
+    if (CAUSAL && p0 + qbase + kFlashBwdQ - 1 < kw) continue;  // every query of the step before every key of this wave
 
     f4 p[2], ds[2];  // [t][r]: query qbase + 16 t + 4g + r, key keyi
 #pragma unroll
@@ -350,7 +395,7 @@ __global__ __launch_bounds__(kFlashThreads) void k_flash_bwd_dkv(const BwdArgs a
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int qi = qbase + 16 * t + 4 * g + r;
-        const bool dead = qi >= S || keyi >= S || (CAUSAL && keyi > qi);
+        const bool dead = qi >= Sq || keyi >= Sk || (CAUSAL && keyi > p0 + qi);
         const float pv = dead ? 0.f : fast_exp2(sa[r] * a.scale_log2 - l4[r]);
         p[t][r] = pv;
         ds[t][r] = pv * (pa[r] - d4[r]);
@@ -363,17 +408,20 @@ __global__ __launch_bounds__(kFlashThreads) void k_flash_bwd_dkv(const BwdArgs a
       dk[dt] = mma32(ld_lds16(Qt + (16 * dt + c) * LDQ + 8 * g), dsf, dk[dt]);
     }
   }
-  if (keyi < S) {
-    const int64_t o = (((int64_t)b * S + keyi) * a.Hkv + hk) * D + 4 * g;
+  if (keyi < Sk) {
+    // self-attention: dk / dv are contiguous [B, S, Hkv, D]
+    const int64_t o = MODE ? 0 : (((int64_t)b * Sk + keyi) * a.Hkv + hk) * D;
+    uint16_t* dkp = a.dk + (MODE ? b * a.sdk.b + hk * a.sdk.h + key_off<SEG>(keyi, a.L, a.dkseg, a.sdk.s) : o) + 4 * g;
+    uint16_t* dvp = a.dv + (MODE ? b * a.sdv.b + hk * a.sdv.h + key_off<SEG>(keyi, a.L, a.dvseg, a.sdv.s) : o) + 4 * g;
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) {
-      st_g8(a.dk + o + 16 * dt, dk[dt], a.scale);
-      st_g8(a.dv + o + 16 * dt, dv[dt], 1.0f);
+      st_g8(dkp + 16 * dt, dk[dt], a.scale);
+      st_g8(dvp + 16 * dt, dv[dt], 1.0f);
     }
   }
 }
 
-template <int D, bool CAUSAL>
+template <int D, bool CAUSAL, int MODE>
 __global__ __launch_bounds__(kFlashThreads) void k_flash_bwd_dq(const BwdArgs a) {
   constexpr int LDK = D + 8, LDT = kFlashBK + 8, KK = D / 32, DT = D / 16, VP = D / 32;
   __shared__ __attribute__((aligned(16))) uint16_t Ks[kFlashBK * LDK];
@@ -381,7 +429,8 @@ __global__ __launch_bounds__(kFlashThreads) void k_flash_bwd_dq(const BwdArgs a)
   __shared__ __attribute__((aligned(16))) uint16_t Kt[D * LDT];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c = lane & 15, g = lane >> 4;
   const int qb = (int)(gridDim.x - 1 - blockIdx.x), h = blockIdx.y, b = blockIdx.z;
-  const int hk = h / (a.Hq / a.Hkv), S = a.S;
+  constexpr bool SEG = MODE == kSegmented;
+  const int hk = h / (a.Hq / a.Hkv), Sq = a.Sq, Sk = MODE ? a.Sk : Sq, p0 = MODE ? a.q_pos0 : 0;  // query row i sits at position p0 + i
   const int q0 = qb * kFlashBQ, qw = q0 + wave * (16 * kFlashQT);
   const uint16_t* qp = a.q + b * a.sq.b + h * a.sq.h;
   const uint16_t* dop = a.dout + b * a.sdo.b + h * a.sdo.h;
@@ -394,28 +443,29 @@ __global__ __launch_bounds__(kFlashThreads) void k_flash_bwd_dq(const BwdArgs a)
 #pragma unroll
   for (int t = 0; t < kFlashQT; ++t) {
     const int qi = qw + 16 * t + c;
-    const bool ok = qi < S;
+    const bool ok = qi < Sq;
 #pragma unroll
     for (int kk = 0; kk < KK; ++kk) {
       qf[t][kk] = as_frag(ld_g16(qp + (int64_t)qi * a.sq.s + 32 * kk + 8 * g, ok));
       dof[t][kk] = as_frag(ld_g16(dop + (int64_t)qi * a.sdo.s + 32 * kk + 8 * g, ok));
     }
-    const int64_t o = ((int64_t)b * a.Hq + h) * S + qi;
+    const int64_t o = ((int64_t)b * a.Hq + h) * Sq + qi;
     lse2[t] = ok ? a.lse[o] * kLog2e : 0.f;
     dl[t] = ok ? a.delta[o] : 0.f;
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) dq[t][dt] = f4{0.f, 0.f, 0.f, 0.f};
   }
 
-  const int kend = CAUSAL ? min(S, q0 + kFlashBQ) : S;
+  const int kend = CAUSAL ? min(Sk, p0 + q0 + kFlashBQ) : Sk;
   const int nt = (kend + kFlashBK - 1) / kFlashBK;
   uint4 kr[VP], vr[VP];
   auto fetch = [&](int key0) {
     const int key = key0 + lane;
+    const int64_t kof = key_off<SEG>(key, a.L, a.kseg, a.sk.s), vof = key_off<SEG>(key, a.L, a.vseg, a.sv.s);
 #pragma unroll
     for (int i = 0; i < VP; ++i) {
-      kr[i] = ld_g16(kp + (int64_t)key * a.sk.s + (wave + 4 * i) * 8, key < S);
-      vr[i] = ld_g16(vp + (int64_t)key * a.sv.s + (wave + 4 * i) * 8, key < S);
+      kr[i] = ld_g16(kp + kof + (wave + 4 * i) * 8, key < Sk);
+      vr[i] = ld_g16(vp + vof + (wave + 4 * i) * 8, key < Sk);
     }
   };
   fetch(0);
@@ -431,7 +481,7 @@ __global__ __launch_bounds__(kFlashThreads) void k_flash_bwd_dq(const BwdArgs a)
     }
     __syncthreads();
     if (it + 1 < nt) fetch(key0 + kFlashBK);
-    if (CAUSAL && key0 > qw + 16 * kFlashQT - 1) continue;
+    if (CAUSAL && key0 > p0 + qw + 16 * kFlashQT - 1) continue;
 
 #pragma unroll
     for (int cc = 0; cc < 2; ++cc) {
@@ -457,7 +507,7 @@ __global__ __launch_bounds__(kFlashThreads) void k_flash_bwd_dq(const BwdArgs a)
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int key = key0 + 16 * kt + 4 * g + r;
-            const bool dead = qi >= S || key >= S || (CAUSAL && key > qi);
+            const bool dead = qi >= Sq || key >= Sk || (CAUSAL && key > p0 + qi);
             const float pv = dead ? 0.f : fast_exp2(sa[r] * a.scale_log2 - lse2[t]);
             ds[u][t][r] = pv * (pa[r] - dl[t]);
           }
@@ -477,8 +527,8 @@ __global__ __launch_bounds__(kFlashThreads) void k_flash_bwd_dq(const BwdArgs a)
 #pragma unroll
   for (int t = 0; t < kFlashQT; ++t) {
     const int qi = qw + 16 * t + c;
-    if (qi >= S) continue;
-    uint16_t* op = a.dq + (((int64_t)b * S + qi) * a.Hq + h) * D + 4 * g;
+    if (qi >= Sq) continue;
+    uint16_t* op = a.dq + (((int64_t)b * Sq + qi) * a.Hq + h) * D + 4 * g;
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) st_g8(op + 16 * dt, dq[t][dt], a.scale);
   }
@@ -497,9 +547,93 @@ void check_shape(int B, int64_t S, int Hq, int Hkv, int D) {
   if (S < 1 || S > (1 << 30)) throw std::invalid_argument("flash_attention: 1 <= S <= 2^30 required");
 }
 
+// The chunk form's own rules: separate lengths, the position of query row 0 and the key segments.
+void check_chunk(int64_t Sq, int64_t Sk, int64_t L, int64_t q_pos0, int Hkv) {
+  if (Sk < 1 || Sk > (1 << 30)) throw std::invalid_argument("flash_attention_chunk: 1 <= Sk <= 2^30 required");
+  if (q_pos0 < 0 || q_pos0 + Sq > (1 << 30))
+    throw std::invalid_argument("flash_attention_chunk: 0 <= q_pos0 and q_pos0 + Sq <= 2^30 required");
+  if (L < 1 || Sk % L) throw std::invalid_argument("flash_attention_chunk: Sk must be a multiple of the segment length");
+  if (Hkv > 65535) throw std::invalid_argument("flash_attention_chunk: Hkv <= 65535 required");
+}
+
+void check_seg(const char* what, int64_t seg) {
+  if (seg % 8) throw std::invalid_argument(std::string("flash_attention_chunk: segment stride of ") + what + " must be a multiple of 8 elements");
+}
+
 template <typename F64, typename F128>
 void by_dim(int D, F64&& f64, F128&& f128) {
   if (D == 64) f64(); else f128();
+}
+
+// One launcher per kernel: the self-attention entry points come here with Sq = Sk, q_pos0 = 0 and
+// L = Sk (kSelf), the chunk entry points with their own values (kChunk, or kSegmented when L < Sk).
+template <int MODE>
+void launch_fwd(const FwdArgs& a, int B, int D, bool causal, hipStream_t st) {
+  const dim3 grid((unsigned)((a.Sq + kFlashBQ - 1) / kFlashBQ), (unsigned)a.Hq, (unsigned)B), block(kFlashThreads);
+  auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, block, 0, st, a); };
+  if (causal) by_dim(D, [&] { go(k_flash_fwd<64, true, MODE>); }, [&] { go(k_flash_fwd<128, true, MODE>); });
+  else by_dim(D, [&] { go(k_flash_fwd<64, false, MODE>); }, [&] { go(k_flash_fwd<128, false, MODE>); });
+}
+
+template <int MODE>
+void launch_bwd(const BwdArgs& a, const uint16_t* outp, float* deltap, int B, int D, bool causal, hipStream_t st) {
+  const dim3 block(kFlashThreads);
+  const int64_t rows = (int64_t)B * a.Sq * a.Hq;
+  const int64_t dblocks = (rows + 16 * (kFlashThreads / 64) - 1) / (16 * (kFlashThreads / 64));
+  if (dblocks > 0x7fffffffLL) throw std::invalid_argument("flash_attention: B * S * Hq too large");
+  by_dim(D,
+         [&] { hipLaunchKernelGGL(k_flash_delta<64>, dim3((unsigned)dblocks), block, 0, st, a.dout, a.sdo, outp, deltap, rows, a.Sq, a.Hq); },
+         [&] { hipLaunchKernelGGL(k_flash_delta<128>, dim3((unsigned)dblocks), block, 0, st, a.dout, a.sdo, outp, deltap, rows, a.Sq, a.Hq); });
+
+  const dim3 gkv((unsigned)((a.Sk + kFlashBK - 1) / kFlashBK), (unsigned)a.Hkv, (unsigned)B);
+  auto gokv = [&](auto kern) { hipLaunchKernelGGL(kern, gkv, block, 0, st, a); };
+  if (causal) by_dim(D, [&] { gokv(k_flash_bwd_dkv<64, true, MODE>); }, [&] { gokv(k_flash_bwd_dkv<128, true, MODE>); });
+  else by_dim(D, [&] { gokv(k_flash_bwd_dkv<64, false, MODE>); }, [&] { gokv(k_flash_bwd_dkv<128, false, MODE>); });
+
+  const dim3 gq((unsigned)((a.Sq + kFlashBQ - 1) / kFlashBQ), (unsigned)a.Hq, (unsigned)B);
+  auto goq = [&](auto kern) { hipLaunchKernelGGL(kern, gq, block, 0, st, a); };
+  if (causal) by_dim(D, [&] { goq(k_flash_bwd_dq<64, true, MODE>); }, [&] { goq(k_flash_bwd_dq<128, true, MODE>); });
+  else by_dim(D, [&] { goq(k_flash_bwd_dq<64, false, MODE>); }, [&] { goq(k_flash_bwd_dq<128, false, MODE>); });
+}
+
+void fill_fwd(FwdArgs& a, uint64_t q, uint64_t k, uint64_t v, uint64_t out, uint64_t lse, int Hq, int Hkv, double scale) {
+  check_view("q", q, a.sq);
+  check_view("k", k, a.sk);
+  check_view("v", v, a.sv);
+  if (out == 0 || out % 16 || lse == 0 || lse % 4) throw std::invalid_argument("flash_attention: misaligned out / lse");
+  a.q = reinterpret_cast<const uint16_t*>(q);
+  a.k = reinterpret_cast<const uint16_t*>(k);
+  a.v = reinterpret_cast<const uint16_t*>(v);
+  a.out = reinterpret_cast<uint16_t*>(out);
+  a.lse = reinterpret_cast<float*>(lse);
+  a.Hq = Hq;
+  a.Hkv = Hkv;
+  a.scale_log2 = (float)(scale * 1.4426950408889634);
+}
+
+void fill_bwd(BwdArgs& a, uint64_t dout, uint64_t q, uint64_t k, uint64_t v, uint64_t out, uint64_t lse, uint64_t delta,
+              uint64_t dq, uint64_t dk, uint64_t dv, int Hq, int Hkv, double scale) {
+  check_view("q", q, a.sq);
+  check_view("k", k, a.sk);
+  check_view("v", v, a.sv);
+  check_view("dout", dout, a.sdo);
+  check_view("dk", dk, a.sdk);
+  check_view("dv", dv, a.sdv);
+  if (out == 0 || (out | dq | dk | dv) % 16 || dq == 0 || dk == 0 || dv == 0 || lse == 0 || delta == 0 || (lse | delta) % 4)
+    throw std::invalid_argument("flash_attention: misaligned out / lse / delta / dq / dk / dv");
+  a.q = reinterpret_cast<const uint16_t*>(q);
+  a.k = reinterpret_cast<const uint16_t*>(k);
+  a.v = reinterpret_cast<const uint16_t*>(v);
+  a.dout = reinterpret_cast<const uint16_t*>(dout);
+  a.lse = reinterpret_cast<const float*>(lse);
+  a.delta = reinterpret_cast<const float*>(delta);
+  a.dq = reinterpret_cast<uint16_t*>(dq);
+  a.dk = reinterpret_cast<uint16_t*>(dk);
+  a.dv = reinterpret_cast<uint16_t*>(dv);
+  a.Hq = Hq;
+  a.Hkv = Hkv;
+  a.scale = (float)scale;
+  a.scale_log2 = (float)(scale * 1.4426950408889634);
 }
 
 void flash_attn_fwd(uint64_t q, uint64_t k, uint64_t v, uint64_t out, uint64_t lse, int64_t q_sb, int64_t q_ss,
@@ -510,24 +644,11 @@ void flash_attn_fwd(uint64_t q, uint64_t k, uint64_t v, uint64_t out, uint64_t l
   a.sq = {q_sb, q_ss, q_sh};
   a.sk = {k_sb, k_ss, k_sh};
   a.sv = {v_sb, v_ss, v_sh};
-  check_view("q", q, a.sq);
-  check_view("k", k, a.sk);
-  check_view("v", v, a.sv);
-  if (out == 0 || out % 16 || lse == 0 || lse % 4) throw std::invalid_argument("flash_attention: misaligned out / lse");
-  a.q = reinterpret_cast<const uint16_t*>(q);
-  a.k = reinterpret_cast<const uint16_t*>(k);
-  a.v = reinterpret_cast<const uint16_t*>(v);
-  a.out = reinterpret_cast<uint16_t*>(out);
-  a.lse = reinterpret_cast<float*>(lse);
-  a.S = (int)S;
-  a.Hq = Hq;
-  a.Hkv = Hkv;
-  a.scale_log2 = (float)(scale * 1.4426950408889634);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const dim3 grid((unsigned)((S + kFlashBQ - 1) / kFlashBQ), (unsigned)Hq, (unsigned)B), block(kFlashThreads);
-  auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, block, 0, st, a); };
-  if (causal) by_dim(D, [&] { go(k_flash_fwd<64, true>); }, [&] { go(k_flash_fwd<128, true>); });
-  else by_dim(D, [&] { go(k_flash_fwd<64, false>); }, [&] { go(k_flash_fwd<128, false>); });
+  a.kseg = a.vseg = 0;
+  fill_fwd(a, q, k, v, out, lse, Hq, Hkv, scale);
+  a.Sq = a.Sk = a.L = (int)S;
+  a.q_pos0 = 0;
+  launch_fwd<kSelf>(a, B, D, causal, reinterpret_cast<hipStream_t>(stream));
   CCMPI_HIP_CHECK(hipGetLastError());
 }
 
@@ -541,47 +662,77 @@ void flash_attn_bwd(uint64_t dout, uint64_t q, uint64_t k, uint64_t v, uint64_t 
   a.sk = {k_sb, k_ss, k_sh};
   a.sv = {v_sb, v_ss, v_sh};
   a.sdo = {do_sb, do_ss, do_sh};
-  check_view("q", q, a.sq);
-  check_view("k", k, a.sk);
-  check_view("v", v, a.sv);
-  check_view("dout", dout, a.sdo);
-  if (out == 0 || (out | dq | dk | dv) % 16 || dq == 0 || dk == 0 || dv == 0 || lse == 0 || delta == 0 || (lse | delta) % 4)
-    throw std::invalid_argument("flash_attention: misaligned out / lse / delta / dq / dk / dv");
-  a.q = reinterpret_cast<const uint16_t*>(q);
-  a.k = reinterpret_cast<const uint16_t*>(k);
-  a.v = reinterpret_cast<const uint16_t*>(v);
-  a.dout = reinterpret_cast<const uint16_t*>(dout);
-  a.lse = reinterpret_cast<const float*>(lse);
-  a.delta = reinterpret_cast<const float*>(delta);
-  a.dq = reinterpret_cast<uint16_t*>(dq);
-  a.dk = reinterpret_cast<uint16_t*>(dk);
-  a.dv = reinterpret_cast<uint16_t*>(dv);
-  a.S = (int)S;
-  a.Hq = Hq;
-  a.Hkv = Hkv;
-  a.scale = (float)scale;
-  a.scale_log2 = (float)(scale * 1.4426950408889634);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const dim3 block(kFlashThreads);
+  a.sdk = a.sdv = {S * Hkv * D, (int64_t)Hkv * D, (int64_t)D};  // contiguous [B, S, Hkv, D]
+  a.kseg = a.vseg = a.dkseg = a.dvseg = 0;
+  fill_bwd(a, dout, q, k, v, out, lse, delta, dq, dk, dv, Hq, Hkv, scale);
+  a.Sq = a.Sk = a.L = (int)S;
+  a.q_pos0 = 0;
+  launch_bwd<kSelf>(a, reinterpret_cast<const uint16_t*>(out), reinterpret_cast<float*>(delta), B, D, causal,
+                    reinterpret_cast<hipStream_t>(stream));
+  CCMPI_HIP_CHECK(hipGetLastError());
+}
 
-  const int64_t rows = (int64_t)B * S * Hq;
-  const int64_t dblocks = (rows + 16 * (kFlashThreads / 64) - 1) / (16 * (kFlashThreads / 64));
-  if (dblocks > 0x7fffffffLL) throw std::invalid_argument("flash_attention: B * S * Hq too large");
+// k / v strides come as (segment, batch, key, head); seg_len = Sk means one run (the segment
+// stride is then unused and the kChunk instantiations run).
+void flash_attn_chunk_fwd(uint64_t q, uint64_t k, uint64_t v, uint64_t out, uint64_t lse, int64_t q_sb, int64_t q_ss,
+                          int64_t q_sh, int64_t k_sg, int64_t k_sb, int64_t k_ss, int64_t k_sh, int64_t v_sg, int64_t v_sb,
+                          int64_t v_ss, int64_t v_sh, int B, int64_t Sq, int64_t Sk, int64_t seg_len, int64_t q_pos0, int Hq,
+                          int Hkv, int D, bool causal, double scale, uint64_t stream) {
+  check_shape(B, Sq, Hq, Hkv, D);
+  check_chunk(Sq, Sk, seg_len, q_pos0, Hkv);
+  FwdArgs a;
+  a.sq = {q_sb, q_ss, q_sh};
+  a.sk = {k_sb, k_ss, k_sh};
+  a.sv = {v_sb, v_ss, v_sh};
+  a.kseg = k_sg;
+  a.vseg = v_sg;
+  check_seg("k", k_sg);
+  check_seg("v", v_sg);
+  fill_fwd(a, q, k, v, out, lse, Hq, Hkv, scale);
+  a.Sq = (int)Sq;
+  a.Sk = (int)Sk;
+  a.L = (int)seg_len;
+  a.q_pos0 = (int)q_pos0;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (seg_len == Sk) launch_fwd<kChunk>(a, B, D, causal, st);
+  else launch_fwd<kSegmented>(a, B, D, causal, st);
+  CCMPI_HIP_CHECK(hipGetLastError());
+}
+
+void flash_attn_chunk_bwd(uint64_t dout, uint64_t q, uint64_t k, uint64_t v, uint64_t out, uint64_t lse, uint64_t delta,
+                          uint64_t dq, uint64_t dk, uint64_t dv, int64_t do_sb, int64_t do_ss, int64_t do_sh, int64_t q_sb,
+                          int64_t q_ss, int64_t q_sh, int64_t k_sg, int64_t k_sb, int64_t k_ss, int64_t k_sh, int64_t v_sg,
+                          int64_t v_sb, int64_t v_ss, int64_t v_sh, int64_t dk_sg, int64_t dk_sb, int64_t dk_ss,
+                          int64_t dk_sh, int64_t dv_sg, int64_t dv_sb, int64_t dv_ss, int64_t dv_sh, int B, int64_t Sq,
+                          int64_t Sk, int64_t seg_len, int64_t q_pos0, int Hq, int Hkv, int D, bool causal, double scale,
+                          uint64_t stream) {
+  check_shape(B, Sq, Hq, Hkv, D);
+  check_chunk(Sq, Sk, seg_len, q_pos0, Hkv);
+  BwdArgs a;
+  a.sq = {q_sb, q_ss, q_sh};
+  a.sk = {k_sb, k_ss, k_sh};
+  a.sv = {v_sb, v_ss, v_sh};
+  a.sdo = {do_sb, do_ss, do_sh};
+  a.sdk = {dk_sb, dk_ss, dk_sh};
+  a.sdv = {dv_sb, dv_ss, dv_sh};
+  a.kseg = k_sg;
+  a.vseg = v_sg;
+  a.dkseg = dk_sg;
+  a.dvseg = dv_sg;
+  check_seg("k", k_sg);
+  check_seg("v", v_sg);
+  check_seg("dk", dk_sg);
+  check_seg("dv", dv_sg);
+  fill_bwd(a, dout, q, k, v, out, lse, delta, dq, dk, dv, Hq, Hkv, scale);
+  a.Sq = (int)Sq;
+  a.Sk = (int)Sk;
+  a.L = (int)seg_len;
+  a.q_pos0 = (int)q_pos0;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const uint16_t* outp = reinterpret_cast<const uint16_t*>(out);
   float* deltap = reinterpret_cast<float*>(delta);
-  by_dim(D,
-         [&] { hipLaunchKernelGGL(k_flash_delta<64>, dim3((unsigned)dblocks), block, 0, st, a.dout, a.sdo, outp, deltap, rows, (int)S, Hq); },
-         [&] { hipLaunchKernelGGL(k_flash_delta<128>, dim3((unsigned)dblocks), block, 0, st, a.dout, a.sdo, outp, deltap, rows, (int)S, Hq); });
-
-  const dim3 gkv((unsigned)((S + kFlashBK - 1) / kFlashBK), (unsigned)Hkv, (unsigned)B);
-  auto gokv = [&](auto kern) { hipLaunchKernelGGL(kern, gkv, block, 0, st, a); };
-  if (causal) by_dim(D, [&] { gokv(k_flash_bwd_dkv<64, true>); }, [&] { gokv(k_flash_bwd_dkv<128, true>); });
-  else by_dim(D, [&] { gokv(k_flash_bwd_dkv<64, false>); }, [&] { gokv(k_flash_bwd_dkv<128, false>); });
-
-  const dim3 gq((unsigned)((S + kFlashBQ - 1) / kFlashBQ), (unsigned)Hq, (unsigned)B);
-  auto goq = [&](auto kern) { hipLaunchKernelGGL(kern, gq, block, 0, st, a); };
-  if (causal) by_dim(D, [&] { goq(k_flash_bwd_dq<64, true>); }, [&] { goq(k_flash_bwd_dq<128, true>); });
-  else by_dim(D, [&] { goq(k_flash_bwd_dq<64, false>); }, [&] { goq(k_flash_bwd_dq<128, false>); });
+  if (seg_len == Sk) launch_bwd<kChunk>(a, outp, deltap, B, D, causal, st);
+  else launch_bwd<kSegmented>(a, outp, deltap, B, D, causal, st);
   CCMPI_HIP_CHECK(hipGetLastError());
 }
 
@@ -606,6 +757,25 @@ void register_flash_attn_ops(pybind11::module_& m) {
         py::arg("q_sb"), py::arg("q_ss"), py::arg("q_sh"), py::arg("k_sb"), py::arg("k_ss"), py::arg("k_sh"),
         py::arg("v_sb"), py::arg("v_ss"), py::arg("v_sh"), py::arg("B"), py::arg("S"), py::arg("Hq"), py::arg("Hkv"),
         py::arg("D"), py::arg("causal"), py::arg("scale"), py::arg("stream"), py::call_guard<py::gil_scoped_release>());
+  m.def("flash_attn_chunk_fwd", &flash_attn_chunk_fwd,
+        "chunk forward: q [B, Sq, Hq, D] at positions q_pos0.., k / v with Sk keys in segments of seg_len (element "
+        "strides segment, b, s, h); causal: key j visible to row i iff j <= q_pos0 + i -> out [B, Sq, Hq, D], lse [B, Hq, Sq]",
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("out"), py::arg("lse"), py::arg("q_sb"), py::arg("q_ss"),
+        py::arg("q_sh"), py::arg("k_sg"), py::arg("k_sb"), py::arg("k_ss"), py::arg("k_sh"), py::arg("v_sg"),
+        py::arg("v_sb"), py::arg("v_ss"), py::arg("v_sh"), py::arg("B"), py::arg("Sq"), py::arg("Sk"), py::arg("seg_len"),
+        py::arg("q_pos0"), py::arg("Hq"), py::arg("Hkv"), py::arg("D"), py::arg("causal"), py::arg("scale"),
+        py::arg("stream"), py::call_guard<py::gil_scoped_release>());
+  m.def("flash_attn_chunk_bwd", &flash_attn_chunk_bwd,
+        "chunk backward: dq [B, Sq, Hq, D] contiguous; dk / dv written through their own (segment, b, s, h) strides; a "
+        "key no query of the chunk sees gets exact zeros",
+        py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("out"), py::arg("lse"), py::arg("delta"),
+        py::arg("dq"), py::arg("dk"), py::arg("dv"), py::arg("do_sb"), py::arg("do_ss"), py::arg("do_sh"),
+        py::arg("q_sb"), py::arg("q_ss"), py::arg("q_sh"), py::arg("k_sg"), py::arg("k_sb"), py::arg("k_ss"),
+        py::arg("k_sh"), py::arg("v_sg"), py::arg("v_sb"), py::arg("v_ss"), py::arg("v_sh"), py::arg("dk_sg"),
+        py::arg("dk_sb"), py::arg("dk_ss"), py::arg("dk_sh"), py::arg("dv_sg"), py::arg("dv_sb"), py::arg("dv_ss"),
+        py::arg("dv_sh"), py::arg("B"), py::arg("Sq"), py::arg("Sk"), py::arg("seg_len"), py::arg("q_pos0"),
+        py::arg("Hq"), py::arg("Hkv"), py::arg("D"), py::arg("causal"), py::arg("scale"), py::arg("stream"),
+        py::call_guard<py::gil_scoped_release>());
 }
 
 }  // namespace dev

@@ -1090,7 +1090,10 @@ class DeviceGroup:
         return dst
 
     @trace_call("reduce_scatter")
-    def reduce_scatter(self, src, dst, op="SUM", algo: str = "direct", max_blocks: Optional[int] = None):
+    def reduce_scatter(self, src, dst, op="SUM", algo: str = "direct", max_blocks: Optional[int] = None,
+                       symmetric: Optional[bool] = None):
+        """``symmetric=True``: as in ``allreduce`` (``src`` a heap block of the same layout on every
+        rank; no host call)."""
         self._check(src, "src")
         self._check(dst, "dst")
         if src.numel() != dst.numel() * self.size:
@@ -1102,16 +1105,19 @@ class DeviceGroup:
             self.dc.rccl_reduce_scatter(src.data_ptr(), dst.data_ptr(), dst.numel(), dt, opc, s)
         else:
             self.dc.reduce_scatter(src.data_ptr(), dst.data_ptr(), dst.numel(), dt, opc, s,
-                                   self._budget(max_blocks), self._symm_call(src.numel() * src.element_size(), src))
+                                   self._budget(max_blocks),
+                                   self._symm_call(src.numel() * src.element_size(), src, promise=symmetric))
         return dst
 
     @trace_call("allgather")
-    def allgather(self, src, dst, algo: str = "direct", max_blocks: Optional[int] = None):
+    def allgather(self, src, dst, algo: str = "direct", max_blocks: Optional[int] = None,
+                  symmetric: Optional[bool] = None):
         """``direct``: every rank pulls every peer's block (input from the
         symmetric heap: zero staging; otherwise staged in chunks); ``push``:
         every rank writes its block into every peer's output (outputs from the
         symmetric heap on every rank; otherwise the pull form); ``auto``: push
-        when the output is symmetric, else direct; ``rccl``."""
+        when the output is symmetric, else direct; ``rccl``.  ``symmetric=True``: as in
+        ``allreduce`` (both tensors heap blocks of the same layout on every rank; no host call)."""
         self._check(src, "src")
         self._check(dst, "dst")
         if dst.numel() != src.numel() * self.size or src.dtype != dst.dtype:
@@ -1123,7 +1129,7 @@ class DeviceGroup:
             self.dc.rccl_allgather(src.data_ptr(), dst.data_ptr(), nb, 1, s)
         elif algo in ("push", "auto", "direct"):
             # one collective decision for the call (registers both tensors when large)
-            symm = self._symm_call(nb * self.size, src, dst)
+            symm = self._symm_call(nb * self.size, src, dst, promise=symmetric)
             if algo in ("push", "auto") and symm and nb % 16 == 0:
                 # push: 0.85x the pull form's time at 64-256 MiB (profiles/r2_coll/allgather_push.md)
                 self.dc.allgather(src.data_ptr(), dst.data_ptr(), nb, s, self._budget(max_blocks), True, self.D.A2A_PUSH)

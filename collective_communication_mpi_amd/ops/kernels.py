@@ -1133,3 +1133,195 @@ def flash_attention(q, k, v, causal: bool = True, scale: Optional[float] = None)
     ``out`` and ``lse``; nothing of size S x S exists."""
     flash_attention_validate(q, k, v)
     return _FlashAttention.apply(q, k, v, bool(causal), scale)[0]
+
+
+# ---------------------------------------------------------------------------
+# chunk form: a query chunk at an offset into a longer, possibly segmented key sequence
+# ---------------------------------------------------------------------------
+_FLASH_MAX_POS = 1 << 30
+
+
+def _flash_kv_view_check(name: str, t, segmented: bool) -> None:
+    """Stride rules of a k / v / dk / dv operand of the chunk form: [B, Sk, Hkv, D], or segmented
+    [n, B, L, Hkv, D]; unit stride on D, every other stride (of an axis longer than 1) a multiple
+    of 8 elements, 16-byte-aligned base."""
+    nd = 5 if segmented else 4
+    if t.stride(nd - 1) != 1:
+        raise ValueError(f"flash_attention_chunk: {name} must have unit stride on the head dim, got strides {t.stride()}")
+    for ax in range(nd - 1):
+        if t.shape[ax] > 1 and t.stride(ax) % 8:
+            what = "the segment stride" if segmented and ax == 0 else f"stride of axis {ax}"
+            raise ValueError(f"flash_attention_chunk: {what} {t.stride(ax)} of {name} is not a multiple of 8 elements")
+    if t.data_ptr() % 16:
+        raise ValueError(f"flash_attention_chunk: {name} must start at a 16-byte-aligned address")
+
+
+def _flash_kv_strides(t, segmented: bool):
+    """(segment, batch, key, head) element strides; 0 for axes of length 1 and for no segments."""
+    st = tuple(t.stride(ax) if t.shape[ax] > 1 else 0 for ax in range(t.dim() - 1))
+    return st if segmented else (0,) + st
+
+
+def flash_attention_chunk_validate(q, k, v, q_pos0: int = 0, kv_segment: Optional[int] = None):
+    """Argument rules of ``flash_attention_chunk`` that need no GPU; raises TypeError (dtypes) /
+    ValueError (everything else) and returns ``(B, Sq, Sk, L, Hq, Hkv, D)``.
+
+    ``q`` is [B, Sq, Hq, D]: query row ``i`` sits at position ``q_pos0 + i`` of the key sequence
+    (``q_pos0 >= 0``, ``q_pos0 + Sq <= 2^30``).  ``kv_segment=None``: ``k`` and ``v`` are
+    [B, Sk, Hkv, D].  ``kv_segment=L``: they are 5-D views [n, B, L, Hkv, D] -- segment ``i`` holds
+    keys ``[i L, (i + 1) L)``, ``Sk = n L`` -- the rank-major layout an all-gather of per-rank
+    [B, L, Hkv, D] shards produces; the segment stride is ``k.stride(0)``.  All bf16 views: unit
+    stride on D, every other stride a multiple of 8 elements, 16-byte-aligned base.  ``Sq`` and
+    ``Sk`` are independent; ``1 <= Sk <= 2^30``."""
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if t.dtype != torch.bfloat16:
+            raise TypeError(f"flash_attention_chunk expects bf16 {name}, got {t.dtype}")
+    if isinstance(q_pos0, bool) or not isinstance(q_pos0, int):
+        raise ValueError(f"flash_attention_chunk: q_pos0 must be an int, got {q_pos0!r}")
+    segmented = kv_segment is not None
+    if segmented and (isinstance(kv_segment, bool) or not isinstance(kv_segment, int) or kv_segment < 1):
+        raise ValueError(f"flash_attention_chunk: kv_segment must be None or a positive int, got {kv_segment!r}")
+    if q.dim() != 4:
+        raise ValueError(f"flash_attention_chunk: q must be [B, Sq, Hq, D], got {tuple(q.shape)}")
+    B, Sq, Hq, D = q.shape
+    if segmented:
+        for name, t in (("k", k), ("v", v)):
+            if t.dim() != 5:
+                raise ValueError(f"flash_attention_chunk: with kv_segment, {name} must be [n, B, L, Hkv, D], got "
+                                 f"{tuple(t.shape)}")
+        n, _, L, Hkv, _ = k.shape
+        want = (n, B, kv_segment, Hkv, D)
+        if L != kv_segment or tuple(k.shape) != want or tuple(v.shape) != want:
+            raise ValueError(f"flash_attention_chunk: k and v must both be [n, B = {B}, L = {kv_segment}, Hkv, D = {D}], "
+                             f"got {tuple(k.shape)} and {tuple(v.shape)}")
+        Sk = n * L
+    else:
+        for name, t in (("k", k), ("v", v)):
+            if t.dim() != 4:
+                raise ValueError(f"flash_attention_chunk: {name} must be [B, Sk, Hkv, D], got {tuple(t.shape)}")
+        _, Sk, Hkv, _ = k.shape
+        L = Sk
+        if tuple(k.shape) != (B, Sk, Hkv, D) or tuple(v.shape) != (B, Sk, Hkv, D):
+            raise ValueError(f"flash_attention_chunk: k and v must both be [B = {B}, Sk, Hkv, D = {D}], got "
+                             f"{tuple(k.shape)} and {tuple(v.shape)}")
+    if D not in FLASH_HEAD_DIMS:
+        raise ValueError(f"flash_attention_chunk: the head dim must be one of {FLASH_HEAD_DIMS}, got {D}")
+    if Sq < 1 or Sk < 1:
+        raise ValueError("flash_attention_chunk: q and k must have at least one position")
+    if Sk > _FLASH_MAX_POS:
+        raise ValueError("flash_attention_chunk: Sk must be at most 2^30")
+    if q_pos0 < 0:
+        raise ValueError(f"flash_attention_chunk: q_pos0 must be >= 0 (key 0 is visible to every row), got {q_pos0}")
+    if q_pos0 + Sq > _FLASH_MAX_POS:
+        raise ValueError("flash_attention_chunk: q_pos0 + Sq must be at most 2^30")
+    if Hkv < 1 or Hq % Hkv:
+        raise ValueError(f"flash_attention_chunk: Hq = {Hq} must be a multiple of Hkv = {Hkv}")
+    if not (1 <= B <= _FLASH_MAX_GRID and Hq <= _FLASH_MAX_GRID):
+        raise ValueError(f"flash_attention_chunk: B and Hq must be in [1, {_FLASH_MAX_GRID}], got {B} and {Hq}")
+    if k.device != q.device or v.device != q.device:
+        raise ValueError("flash_attention_chunk: q, k and v must be on one device")
+    _flash_view_check("q", q)
+    _flash_kv_view_check("k", k, segmented)
+    _flash_kv_view_check("v", v, segmented)
+    return int(B), int(Sq), int(Sk), int(L), int(Hq), int(Hkv), int(D)
+
+
+def _flash_kv_result(name: str, t, like_k, segmented: bool):
+    """A caller's dk / dv of the chunk form: the shape of ``k`` (5-D on the segmented path), bf16,
+    on its device, under the view rules of ``k``; allocated contiguous when not given."""
+    if t is None:
+        return torch.empty(like_k.shape, dtype=torch.bfloat16, device=like_k.device)
+    if t.dtype != torch.bfloat16:
+        raise TypeError(f"flash_attention_chunk: {name} must be bf16, got {t.dtype}")
+    if tuple(t.shape) != tuple(like_k.shape) or t.device != like_k.device:
+        raise ValueError(f"flash_attention_chunk: {name} must be a {tuple(like_k.shape)} tensor on {like_k.device}, got "
+                         f"{tuple(t.shape)}")
+    _flash_kv_view_check(name, t, segmented)
+    return t
+
+
+def flash_attention_chunk_forward(q, k, v, causal: bool = True, scale: Optional[float] = None, out=None, lse=None, *,
+                                  q_pos0: int = 0, kv_segment: Optional[int] = None):
+    """``flash_attention_forward`` for a query chunk ``q`` [B, Sq, Hq, D] whose row 0 sits at
+    position ``q_pos0`` of a key sequence of its own length ``Sk``: with ``causal``, key ``j`` is
+    visible to row ``i`` iff ``j <= q_pos0 + i`` (``q_pos0`` is ignored without).  ``k`` / ``v`` as
+    ``flash_attention_chunk_validate`` describes, segmented or not.  Returns ``(out [B, Sq, Hq, D]
+    bf16 contiguous, lse [B, Hq, Sq] fp32)``; for a chunk of a self-attention call these are bitwise
+    the full call's rows.  No host synchronisation, and no allocation when ``out`` and ``lse`` are
+    passed."""
+    B, Sq, Sk, L, Hq, Hkv, D = flash_attention_chunk_validate(q, k, v, q_pos0, kv_segment)
+    seg = kv_segment is not None
+    sc = _flash_scale(scale, D)
+    out = _flash_result("out", out, (B, Sq, Hq, D), torch.bfloat16, q)
+    lse = _flash_result("lse", lse, (B, Hq, Sq), torch.float32, q)
+    _D().flash_attn_chunk_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr(),
+                              *_flash_strides(q), *_flash_kv_strides(k, seg), *_flash_kv_strides(v, seg), B, Sq, Sk, L,
+                              q_pos0, Hq, Hkv, D, bool(causal), sc, _stream(q))
+    return out, lse
+
+
+def flash_attention_chunk_backward(dout, q, k, v, out, lse, causal: bool = True, scale: Optional[float] = None,
+                                   dq=None, dk=None, dv=None, delta=None, *, q_pos0: int = 0,
+                                   kv_segment: Optional[int] = None):
+    """``(dq, dk, dv)`` of ``flash_attention_chunk_forward``.  ``dq`` [B, Sq, Hq, D] bf16
+    contiguous; ``dk`` / ``dv`` have the shape of ``k`` (5-D on the segmented path) and are written
+    through their own strides under the view rules of ``k``, so they may be views of a larger
+    buffer (the send buffer of a reduce-scatter); they hold this chunk's share only, and a key
+    that no query of the chunk sees gets exact zeros.  ``delta`` [B, Hq, Sq] fp32 is the
+    workspace.  With ``dq``, ``dk``, ``dv`` and ``delta`` passed the call allocates nothing."""
+    B, Sq, Sk, L, Hq, Hkv, D = flash_attention_chunk_validate(q, k, v, q_pos0, kv_segment)
+    seg = kv_segment is not None
+    sc = _flash_scale(scale, D)
+    if dout.dtype != torch.bfloat16:
+        raise TypeError(f"flash_attention_chunk expects bf16 dout, got {dout.dtype}")
+    if tuple(dout.shape) != (B, Sq, Hq, D) or dout.device != q.device:
+        raise ValueError(f"flash_attention_chunk: dout must be {(B, Sq, Hq, D)} on {q.device}, got {tuple(dout.shape)}")
+    _flash_view_check("dout", dout)
+    if out is None or lse is None:
+        raise ValueError("flash_attention_chunk_backward needs the forward's out and lse")
+    out = _flash_result("out", out, (B, Sq, Hq, D), torch.bfloat16, q)
+    lse = _flash_result("lse", lse, (B, Hq, Sq), torch.float32, q)
+    # every caller-provided result is checked before anything is allocated or launched
+    for name, t in (("dk", dk), ("dv", dv)):
+        if t is not None:
+            _flash_kv_result(name, t, k, seg)
+    dq = _flash_result("dq", dq, (B, Sq, Hq, D), torch.bfloat16, q)
+    delta = _flash_result("delta", delta, (B, Hq, Sq), torch.float32, q)
+    dk = _flash_kv_result("dk", dk, k, seg)
+    dv = _flash_kv_result("dv", dv, k, seg)
+    _D().flash_attn_chunk_bwd(dout.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr(),
+                              delta.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), *_flash_strides(dout),
+                              *_flash_strides(q), *_flash_kv_strides(k, seg), *_flash_kv_strides(v, seg),
+                              *_flash_kv_strides(dk, seg), *_flash_kv_strides(dv, seg), B, Sq, Sk, L, q_pos0, Hq, Hkv, D,
+                              bool(causal), sc, _stream(q))
+    return dq, dk, dv
+
+
+class _FlashAttentionChunk(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, causal, scale, q_pos0, kv_segment):
+        out, lse = flash_attention_chunk_forward(q, k, v, causal, scale, q_pos0=q_pos0, kv_segment=kv_segment)
+        ctx.save_for_backward(q, k, v, out, lse)
+        ctx.args = (causal, scale, q_pos0, kv_segment)
+        ctx.mark_non_differentiable(lse)
+        return out, lse
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout, _dlse):
+        q, k, v, out, lse = ctx.saved_tensors
+        causal, scale, q_pos0, kv_segment = ctx.args
+        if not _flash_is_view(dout):
+            dout = dout.contiguous()
+        dq, dk, dv = flash_attention_chunk_backward(dout, q, k, v, out, lse, causal, scale, q_pos0=q_pos0,
+                                                    kv_segment=kv_segment)
+        return dq, dk, dv, None, None, None, None
+
+
+def flash_attention_chunk(q, k, v, causal: bool = True, scale: Optional[float] = None, *, q_pos0: int = 0,
+                          kv_segment: Optional[int] = None):
+    """Differentiable ``flash_attention_chunk_forward``: ``out`` [B, Sq, Hq, D] bf16, differentiable
+    in ``q``, ``k`` and ``v``; the gradients of ``k`` and ``v`` have their shape (5-D when
+    segmented) and are this chunk's share."""
+    flash_attention_chunk_validate(q, k, v, q_pos0, kv_segment)
+    return _FlashAttentionChunk.apply(q, k, v, bool(causal), scale, q_pos0, kv_segment)[0]

@@ -22,3 +22,8 @@ from .tensor_parallel import (  # noqa: F401,E402
 )
 from .moe_experts import GroupedExpertsMLP  # noqa: F401,E402
 from .moe import RoutedMoE, moe_combine, moe_dispatch  # noqa: F401,E402
+from .context_parallel import (  # noqa: F401,E402
+    context_parallel_attention,
+    context_parallel_attention_backward,
+    context_parallel_attention_forward,
+)

@@ -18,6 +18,11 @@ star adds on that communicator.  Attention is chosen by ``LlamaConfig.attention`
 ``repeat_interleave``; "flash" is the project's own kernel (``ops.flash_attention``,
 csrc/device/flash_attn.hip), which reads the projections' [B, S, H, hd] views as they are,
 never expands K or V and writes the [B * S, d] input of ``wo`` directly (head dim 64 or 128).
+With ``cp`` (a communicator) and "flash" the sequence axis is split: every rank of ``cp`` runs the
+model on its shard of consecutive positions and the block calls ``context_parallel_attention``
+(parallel/context_parallel.py); everything else in the block is per token.  The caller passes
+explicit ``targets`` (a shard's last target lives on the next rank) and averages the parameter
+gradients over ``cp``.
 RoPE is left out (no effect on gradient sizes or the GEMM work).  Random-init weights,
 synthetic token ids.
 """
@@ -31,6 +36,7 @@ import torch
 import torch.nn.functional as F
 
 from ..ops.kernels import FLASH_HEAD_DIMS, flash_attention
+from .context_parallel import context_parallel_attention
 from .ddp import DistributedDataParallel
 from .tensor_parallel import ColumnParallelLinear, ParallelSwiGLUMLP, RowParallelLinear
 
@@ -71,14 +77,17 @@ class RMSNorm(torch.nn.Module):
 
 
 class LlamaBlock(torch.nn.Module):
-    def __init__(self, cfg: LlamaConfig, tp, seed: int, device, dtype=torch.bfloat16):
+    def __init__(self, cfg: LlamaConfig, tp, seed: int, device, dtype=torch.bfloat16, cp=None):
         super().__init__()
         d, kv = cfg.d, cfg.kv_heads * cfg.head_dim
         self.cfg = cfg
+        self.cp = cp  # context-parallel communicator: x holds this rank's shard of the sequence
         if cfg.attention not in ATTENTION_KINDS:
             raise ValueError(f"LlamaConfig.attention must be one of {ATTENTION_KINDS}, got {cfg.attention!r}")
         if cfg.attention == "flash" and cfg.head_dim not in FLASH_HEAD_DIMS:
             raise ValueError(f'attention="flash" needs a head dim in {FLASH_HEAD_DIMS}, got {cfg.head_dim}')
+        if cp is not None and cfg.attention != "flash":
+            raise ValueError(f'context parallelism (cp) needs attention="flash", got {cfg.attention!r}')
         kw = dict(bias=False, device=device, dtype=dtype, init="device")
         self.attn_norm = RMSNorm(d, cfg.eps, device, dtype)
         self.wq = ColumnParallelLinear(d, d, tp, seed=seed, **kw)
@@ -93,8 +102,12 @@ class LlamaBlock(torch.nn.Module):
         hd = cfg.head_dim
         n = self.attn_norm(x)
         if cfg.attention == "flash":  # the projections' views as they are; K and V stay at kv_heads
-            o = flash_attention(self.wq(n).view(batch, seq, cfg.heads, hd), self.wk(n).view(batch, seq, cfg.kv_heads, hd),
-                                self.wv(n).view(batch, seq, cfg.kv_heads, hd), causal=True)
+            q, k, v = (self.wq(n).view(batch, seq, cfg.heads, hd), self.wk(n).view(batch, seq, cfg.kv_heads, hd),
+                       self.wv(n).view(batch, seq, cfg.kv_heads, hd))
+            if self.cp is not None:  # seq is this rank's shard; K | V of the other shards are gathered
+                o = context_parallel_attention(self.cp, q, k, v, causal=True)
+            else:
+                o = flash_attention(q, k, v, causal=True)
             h = x + self.wo(o.view(batch * seq, cfg.d))
             return h + self.mlp(self.mlp_norm(h))
         q = self.wq(n).view(batch, seq, cfg.heads, hd).transpose(1, 2)
@@ -111,9 +124,11 @@ class LlamaBlock(torch.nn.Module):
 
 
 class LlamaModel(torch.nn.Module):
-    """Token ids [batch, seq] -> mean next-token cross-entropy (fp32)."""
+    """Token ids [batch, seq] -> mean next-token cross-entropy (fp32).  With ``cp``, ``ids`` (and
+    ``targets``) are this rank's shard of consecutive positions and the loss is the shard's mean."""
 
-    def __init__(self, cfg: LlamaConfig, tp, device, dtype=torch.bfloat16, seed: int = 0, vocab: bool = True):
+    def __init__(self, cfg: LlamaConfig, tp, device, dtype=torch.bfloat16, seed: int = 0, vocab: bool = True,
+                 cp=None):
         super().__init__()
         self.cfg = cfg
         self.vocab = vocab
@@ -122,14 +137,14 @@ class LlamaModel(torch.nn.Module):
             with torch.no_grad():
                 g = torch.Generator(device=device).manual_seed(seed)
                 self.embed.weight.normal_(0.0, 0.02, generator=g)
-        self.blocks = torch.nn.ModuleList(LlamaBlock(cfg, tp, seed + 10 * (i + 1), device, dtype)
+        self.blocks = torch.nn.ModuleList(LlamaBlock(cfg, tp, seed + 10 * (i + 1), device, dtype, cp=cp)
                                           for i in range(cfg.layers))
         self.norm = RMSNorm(cfg.d, cfg.eps, device, dtype)
         if vocab:
             self.head = ColumnParallelLinear(cfg.d, cfg.vocab, tp, bias=False, device=device, dtype=dtype,
                                              seed=seed + 7, init="device")
 
-    def forward(self, ids, x0: Optional[torch.Tensor] = None):
+    def forward(self, ids, x0: Optional[torch.Tensor] = None, targets: Optional[torch.Tensor] = None):
         b, s = ids.shape
         x = self.embed(ids).view(b * s, self.cfg.d) if self.vocab else x0
         for blk in self.blocks:
@@ -138,7 +153,9 @@ class LlamaModel(torch.nn.Module):
         if not self.vocab:
             return x.float().pow(2).mean()
         logits = self.head(x)
-        tgt = torch.roll(ids, -1, dims=1).reshape(-1)
+        # explicit targets [batch, seq] replace the roll (context parallel: a shard's last target is
+        # the next rank's first id)
+        tgt = (torch.roll(ids, -1, dims=1) if targets is None else targets).reshape(-1)
         return F.cross_entropy(logits.float(), tgt)
 
 
