@@ -33,20 +33,25 @@
 //                    S^T, dP^T with the query on the lane, dQ^T += K^T dS^T.
 // Chunk form (ops.flash_attention_chunk, the kernels of parallel/context_parallel.py): the same four
 // kernels with separate lengths Sq (rows of q, dout, out, dq, lse, delta) and Sk (rows of k, v, dk,
-// dv) and the position q_pos0 >= 0 of query row 0; causal: key j is visible to row i iff
-// j <= q_pos0 + i, so key 0 is visible to every row and no row is ever fully masked.  Every skip
-// rule moves with the offset: the forward / dQ key loop ends at min(Sk, q_pos0 + q0 + kFlashBQ), a
-// wave skips steps above q_pos0 + its last row, the dK/dV kernel starts at query step
-// max(0, key0 - q_pos0) / kFlashBwdQ, and a key block no query of the chunk sees has zero steps and
-// stores exact zeros (a reduce-scatter sums it).  A row's sums run over the same key steps in the
-// same order whichever chunk holds it and a wholly masked step is an exact no-op (alpha = 1,
-// p = 0), so out, lse and dq of a chunk are bitwise the full call's rows.  SEG: the key axis of
-// k / v / dk / dv is cut into segments of L keys (Sk % L == 0), key j at (j / L) * seg + (j % L) * s,
-// each tensor with strides of its own: [n, B, L, Hkv, D], the layout an all-gather of per-rank
-// shards produces.  The map is applied per key row in every fetch and store, so a tile may
-// straddle segments; keys >= Sk and whatever lies between segments are never touched.  Self-attention
-// is the kSelf instantiation of the same kernels, where Sq = Sk and q_pos0 = 0 are compile-time facts:
-// the code, the speed and the bits it always had.
+// dv) and the position q_pos0 >= 0 of query row 0.
+//
+// THE MASK has one home, struct Mask below: key j is visible to query row i iff j < Sk, i < Sq
+// and, when causal, j <= q_pos0 + i; so key 0 is visible to every row and no row is ever fully
+// masked.  Every skip is that rule applied to a block and is a member of Mask, used by all three
+// kernels: the end of the forward / dQ key loop, the step a wave skips, the forward's edge test,
+// the first query step of the dK/dV kernel.  A key block no query of the chunk sees has zero
+// steps and stores exact zeros (a reduce-scatter sums it).  A row's sums run over the same key
+// steps in the same order whichever chunk holds it and a wholly masked step is an exact no-op
+// (alpha = 1, p = 0), so out, lse and dq of a chunk are bitwise the full call's rows.
+//
+// SEG: the key axis of k / v / dk / dv is cut into segments of L keys (Sk % L == 0), key j at
+// (j / L) * seg + (j % L) * s, each tensor with strides of its own: [n, B, L, Hkv, D], the layout
+// an all-gather of per-rank shards produces.  The map is applied per key row in every fetch and
+// store, so a tile may straddle segments; keys >= Sk and whatever lies between segments are never
+// touched.  Self-attention is the kSelf instantiation of the same kernels, where Sq = Sk and
+// q_pos0 = 0 are compile-time facts: the code, the speed and the bits it always had.  Which
+// instantiation runs is the caller's choice (the self_attention flag of the two entry points), not
+// a property of the values: a chunk call with Sq = Sk and q_pos0 = 0 still runs kChunk.
 //
 // P is recomputed in both backward kernels (seven products per tile pair instead of five): no
 // atomics, no hand-off between workgroups, every sum has one owner and a fixed order, so all
@@ -57,6 +62,8 @@
 #include <cmath>
 #include <stdexcept>
 #include <string>
+#include <tuple>
+#include <type_traits>
 
 #include "common.hpp"
 #include "flash_attn.hpp"
@@ -118,6 +125,31 @@ __device__ __forceinline__ int64_t key_off(int key, int L, int64_t seg, int64_t 
   return (int64_t)n * seg + (int64_t)(key - n * L) * s;
 }
 
+// The mask, and everything a kernel concludes from it.  Query row qi sits at position p0 + qi of
+// the key sequence; key `key` is visible to it iff both exist and, under CAUSAL, key <= p0 + qi.
+// Every skip below is that one rule (`above`) applied to the corner of a block of rows and keys.
+template <bool CAUSAL, int MODE>
+struct Mask {
+  int Sq, Sk, p0;
+  template <typename Args>
+  __device__ __forceinline__ explicit Mask(const Args& a) : Sq(a.Sq), Sk(MODE ? a.Sk : a.Sq), p0(MODE ? a.q_pos0 : 0) {}
+  // key lies above the diagonal of row qi + d
+  __device__ __forceinline__ bool above(int qi, int key, int d = 0) const { return CAUSAL && key > p0 + qi + d; }
+  // rows past Sq are computed and never stored, so the forward leaves the row test out
+  __device__ __forceinline__ bool key_masked(int qi, int key) const { return key >= Sk || above(qi, key); }
+  __device__ __forceinline__ bool masked(int qi, int key) const { return qi >= Sq || key >= Sk || above(qi, key); }
+  // the `rows` rows from q_first see no key >= key_first: a wave skips the step
+  __device__ __forceinline__ bool none_visible(int q_first, int rows, int key_first) const { return above(q_first, key_first, rows - 1); }
+  // some row >= q_first does not see some key < key_end: the step needs the per-element test
+  __device__ __forceinline__ bool edge(int q_first, int key_end) const { return key_end > Sk || above(q_first, key_end - 1); }
+  // forward / dQ: end of the key loop of the kFlashBQ rows from q0 (tiles above the diagonal are skipped)
+  __device__ __forceinline__ int key_end(int q0) const { return CAUSAL ? min(Sk, p0 + q0 + kFlashBQ) : Sk; }
+  // dK/dV: first kFlashBwdQ-row query step that sees a key >= key0; it may lie past Sq (no steps)
+  __device__ __forceinline__ int first_query_step(int key0) const {
+    return CAUSAL ? (MODE ? max(0, key0 - p0) : key0) / kFlashBwdQ : 0;
+  }
+};
+
 __device__ __forceinline__ f4 mma32(bf16x8 a, bf16x8 b, f4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
@@ -146,6 +178,12 @@ __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_ex
 __device__ __forceinline__ void st_g8(uint16_t* p, f4 v, float mul) {
   *reinterpret_cast<uint2*>(p) = uint2{pk_bf16(v[0] * mul, v[1] * mul), pk_bf16(v[2] * mul, v[3] * mul)};
 }
+// Operand fragment kk of query row qi for a product with the query on the MFMA column, from q or
+// dout (`p` at the batch and head, row stride `s`; zeros where !ok): the prologue of the forward
+// and dQ kernels.
+__device__ __forceinline__ bf16x8 ld_query_frag(const uint16_t* p, int64_t s, int qi, int kk, int g, bool ok) {
+  return as_frag(ld_g16(p + (int64_t)qi * s + 32 * kk + 8 * g, ok));
+}
 
 template <int D, bool CAUSAL, int MODE>
 __global__ __launch_bounds__(kFlashThreads) void k_flash_fwd(const FwdArgs a) {
@@ -156,7 +194,8 @@ __global__ __launch_bounds__(kFlashThreads) void k_flash_fwd(const FwdArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c = lane & 15, g = lane >> 4;
   const int qb = (int)(gridDim.x - 1 - blockIdx.x), h = blockIdx.y, b = blockIdx.z;  // heaviest blocks first
   constexpr bool SEG = MODE == kSegmented;
-  const int hk = h / (a.Hq / a.Hkv), Sq = a.Sq, Sk = MODE ? a.Sk : Sq, p0 = MODE ? a.q_pos0 : 0;  // query row i sits at position p0 + i
+  const Mask<CAUSAL, MODE> mask(a);
+  const int hk = h / (a.Hq / a.Hkv), Sq = mask.Sq, Sk = mask.Sk;
   const int q0 = qb * kFlashBQ, qw = q0 + wave * (16 * kFlashQT);
   const uint16_t* qp = a.q + b * a.sq.b + h * a.sq.h;
   const uint16_t* kp = a.k + b * a.sk.b + hk * a.sk.h;
@@ -167,7 +206,7 @@ __global__ __launch_bounds__(kFlashThreads) void k_flash_fwd(const FwdArgs a) {
   for (int t = 0; t < kFlashQT; ++t) {
     const int qi = qw + 16 * t + c;
 #pragma unroll
-    for (int kk = 0; kk < KK; ++kk) qf[t][kk] = as_frag(ld_g16(qp + (int64_t)qi * a.sq.s + 32 * kk + 8 * g, qi < Sq));
+    for (int kk = 0; kk < KK; ++kk) qf[t][kk] = ld_query_frag(qp, a.sq.s, qi, kk, g, qi < Sq);
   }
   f4 o[kFlashQT][DT];
   float m[kFlashQT], l[kFlashQT];
@@ -179,8 +218,7 @@ __global__ __launch_bounds__(kFlashThreads) void k_flash_fwd(const FwdArgs a) {
     for (int dt = 0; dt < DT; ++dt) o[t][dt] = f4{0.f, 0.f, 0.f, 0.f};
   }
 
-  const int kend = CAUSAL ? min(Sk, p0 + q0 + kFlashBQ) : Sk;
-  const int nt = (kend + kFlashBK - 1) / kFlashBK;
+  const int nt = (mask.key_end(q0) + kFlashBK - 1) / kFlashBK;
   uint4 kr[KP], vr[VP];
   auto fetch = [&](int key0) {
 #pragma unroll
@@ -207,7 +245,7 @@ __global__ __launch_bounds__(kFlashThreads) void k_flash_fwd(const FwdArgs a) {
     for (int i = 0; i < VP; ++i) st_transposed(Vt, LDT, (wave + 4 * i) * 8, perm64(lane), vr[i]);
     __syncthreads();
     if (it + 1 < nt) fetch(key0 + kFlashBK);
-    if (CAUSAL && key0 > p0 + qw + 16 * kFlashQT - 1) continue;  // every key above every row of this wave
+    if (mask.none_visible(qw, 16 * kFlashQT, key0)) continue;  // every key above every row of this wave
 
     f4 s[4][kFlashQT];  // s[kt][t][r] = score of key key0 + 16 kt + 4g + r, query qw + 16 t + c
 #pragma unroll
@@ -223,7 +261,7 @@ __global__ __launch_bounds__(kFlashThreads) void k_flash_fwd(const FwdArgs a) {
         s[kt][t] = acc;
       }
     }
-    const bool edge = key0 + kFlashBK > Sk || (CAUSAL && key0 + kFlashBK - 1 > p0 + qw);
+    const bool edge = mask.edge(qw, key0 + kFlashBK);
 #pragma unroll
     for (int t = 0; t < kFlashQT; ++t) {
       const int qi = qw + 16 * t + c;
@@ -235,7 +273,7 @@ __global__ __launch_bounds__(kFlashThreads) void k_flash_fwd(const FwdArgs a) {
           float x = s[kt][t][r] * a.scale_log2;
           if (edge) {
             const int key = key0 + 16 * kt + 4 * g + r;
-            if (key >= Sk || (CAUSAL && key > p0 + qi)) x = -INFINITY;
+            if (mask.key_masked(qi, key)) x = -INFINITY;
           }
           s[kt][t][r] = x;
           mx = fmaxf(mx, x);
@@ -323,7 +361,8 @@ __global__ __launch_bounds__(kFlashThreads) void k_flash_bwd_dkv(const BwdArgs a
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c = lane & 15, g = lane >> 4;
   const int kb = blockIdx.x, hk = blockIdx.y, b = blockIdx.z;
   constexpr bool SEG = MODE == kSegmented;
-  const int Sq = a.Sq, Sk = MODE ? a.Sk : Sq, p0 = MODE ? a.q_pos0 : 0, rep = a.Hq / a.Hkv;
+  const Mask<CAUSAL, MODE> mask(a);
+  const int Sq = mask.Sq, Sk = mask.Sk, rep = a.Hq / a.Hkv;
   const int key0 = kb * kFlashBK, kw = key0 + 16 * wave, keyi = kw + c;
   const uint16_t* kp = a.k + b * a.sk.b + hk * a.sk.h + key_off<SEG>(keyi, a.L, a.kseg, a.sk.s);
   const uint16_t* vp = a.v + b * a.sv.b + hk * a.sv.h + key_off<SEG>(keyi, a.L, a.vseg, a.sv.s);
@@ -339,7 +378,7 @@ __global__ __launch_bounds__(kFlashThreads) void k_flash_bwd_dkv(const BwdArgs a
 
   // query steps wholly before the key block see none of it; a key block past every query of the
   // chunk has no step at all and stores exact zeros
-  const int qs0 = CAUSAL ? (MODE ? max(0, key0 - p0) : key0) / kFlashBwdQ : 0;
+  const int qs0 = mask.first_query_step(key0);
   const int nqs = (Sq + kFlashBwdQ - 1) / kFlashBwdQ - qs0, nq = MODE ? max(0, nqs) : nqs;
   const int steps = rep * nq;  // query heads in order, query steps in order inside each
   const int row = tid & 31, cb = tid >> 5;
@@ -379,7 +418,7 @@ __global__ __launch_bounds__(kFlashThreads) void k_flash_bwd_dkv(const BwdArgs a
     }
     __syncthreads();
     if (i + 1 < steps) fetch(i + 1);
-    if (CAUSAL && p0 + qbase + kFlashBwdQ - 1 < kw) continue;  // every query of the step before every key of this wave
+    if (mask.none_visible(qbase, kFlashBwdQ, kw)) continue;  // every query of the step before every key of this wave
 
     f4 p[2], ds[2];  // [t][r]: query qbase + 16 t + 4g + r, key keyi
 #pragma unroll
@@ -395,8 +434,7 @@ __global__ __launch_bounds__(kFlashThreads) void k_flash_bwd_dkv(const BwdArgs a
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int qi = qbase + 16 * t + 4 * g + r;
-        const bool dead = qi >= Sq || keyi >= Sk || (CAUSAL && keyi > p0 + qi);
-        const float pv = dead ? 0.f : fast_exp2(sa[r] * a.scale_log2 - l4[r]);
+        const float pv = mask.masked(qi, keyi) ? 0.f : fast_exp2(sa[r] * a.scale_log2 - l4[r]);
         p[t][r] = pv;
         ds[t][r] = pv * (pa[r] - d4[r]);
       }
@@ -430,7 +468,8 @@ __global__ __launch_bounds__(kFlashThreads) void k_flash_bwd_dq(const BwdArgs a)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c = lane & 15, g = lane >> 4;
   const int qb = (int)(gridDim.x - 1 - blockIdx.x), h = blockIdx.y, b = blockIdx.z;
   constexpr bool SEG = MODE == kSegmented;
-  const int hk = h / (a.Hq / a.Hkv), Sq = a.Sq, Sk = MODE ? a.Sk : Sq, p0 = MODE ? a.q_pos0 : 0;  // query row i sits at position p0 + i
+  const Mask<CAUSAL, MODE> mask(a);
+  const int hk = h / (a.Hq / a.Hkv), Sq = mask.Sq, Sk = mask.Sk;
   const int q0 = qb * kFlashBQ, qw = q0 + wave * (16 * kFlashQT);
   const uint16_t* qp = a.q + b * a.sq.b + h * a.sq.h;
   const uint16_t* dop = a.dout + b * a.sdo.b + h * a.sdo.h;
@@ -446,8 +485,8 @@ __global__ __launch_bounds__(kFlashThreads) void k_flash_bwd_dq(const BwdArgs a)
     const bool ok = qi < Sq;
 #pragma unroll
     for (int kk = 0; kk < KK; ++kk) {
-      qf[t][kk] = as_frag(ld_g16(qp + (int64_t)qi * a.sq.s + 32 * kk + 8 * g, ok));
-      dof[t][kk] = as_frag(ld_g16(dop + (int64_t)qi * a.sdo.s + 32 * kk + 8 * g, ok));
+      qf[t][kk] = ld_query_frag(qp, a.sq.s, qi, kk, g, ok);
+      dof[t][kk] = ld_query_frag(dop, a.sdo.s, qi, kk, g, ok);
     }
     const int64_t o = ((int64_t)b * a.Hq + h) * Sq + qi;
     lse2[t] = ok ? a.lse[o] * kLog2e : 0.f;
@@ -456,8 +495,7 @@ __global__ __launch_bounds__(kFlashThreads) void k_flash_bwd_dq(const BwdArgs a)
     for (int dt = 0; dt < DT; ++dt) dq[t][dt] = f4{0.f, 0.f, 0.f, 0.f};
   }
 
-  const int kend = CAUSAL ? min(Sk, p0 + q0 + kFlashBQ) : Sk;
-  const int nt = (kend + kFlashBK - 1) / kFlashBK;
+  const int nt = (mask.key_end(q0) + kFlashBK - 1) / kFlashBK;
   uint4 kr[VP], vr[VP];
   auto fetch = [&](int key0) {
     const int key = key0 + lane;
@@ -481,7 +519,7 @@ __global__ __launch_bounds__(kFlashThreads) void k_flash_bwd_dq(const BwdArgs a)
     }
     __syncthreads();
     if (it + 1 < nt) fetch(key0 + kFlashBK);
-    if (CAUSAL && key0 > p0 + qw + 16 * kFlashQT - 1) continue;
+    if (mask.none_visible(qw, 16 * kFlashQT, key0)) continue;
 
 #pragma unroll
     for (int cc = 0; cc < 2; ++cc) {
@@ -507,8 +545,7 @@ __global__ __launch_bounds__(kFlashThreads) void k_flash_bwd_dq(const BwdArgs a)
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int key = key0 + 16 * kt + 4 * g + r;
-            const bool dead = qi >= Sq || key >= Sk || (CAUSAL && key > p0 + qi);
-            const float pv = dead ? 0.f : fast_exp2(sa[r] * a.scale_log2 - lse2[t]);
+            const float pv = mask.masked(qi, key) ? 0.f : fast_exp2(sa[r] * a.scale_log2 - lse2[t]);
             ds[u][t][r] = pv * (pa[r] - dl[t]);
           }
         }
@@ -534,205 +571,135 @@ __global__ __launch_bounds__(kFlashThreads) void k_flash_bwd_dq(const BwdArgs a)
   }
 }
 
-void check_view(const char* what, uint64_t p, const Strides& s) {
-  if (p == 0 || p % 16) throw std::invalid_argument(std::string("flash_attention: ") + what + " must be 16-byte aligned");
-  if (s.b % 8 || s.s % 8 || s.h % 8)
-    throw std::invalid_argument(std::string("flash_attention: ") + what + " strides must be multiples of 8 elements");
+// One strided operand as the binding takes it: (address, segment stride, batch, row and head stride),
+// strides in elements; the segment stride is 0 where the key axis is one run.
+using View = std::tuple<uint64_t, int64_t, int64_t, int64_t, int64_t>;
+
+struct Problem {
+  int B;
+  int64_t Sq, Sk, L, q_pos0;  // L: keys per segment, = Sk for one run
+  int Hq, Hkv, D;
+  bool causal;
+  double scale;
+  bool self;  // the caller's flag: run kSelf
+};
+
+[[noreturn]] void refuse(const std::string& what) { throw std::invalid_argument("flash_attention: " + what); }
+
+void check(const Problem& p) {
+  if (p.D != 64 && p.D != 128) refuse("head dim must be 64 or 128");
+  if (p.B < 1 || p.B > 65535 || p.Hq < 1 || p.Hq > 65535) refuse("1 <= B, Hq <= 65535 required");
+  if (p.Hkv < 1 || p.Hq % p.Hkv) refuse("Hq must be a multiple of Hkv");
+  if (p.Sq < 1 || p.Sq > (1 << 30) || p.Sk < 1 || p.Sk > (1 << 30)) refuse("1 <= Sq, Sk <= 2^30 required");
+  if (p.q_pos0 < 0 || p.q_pos0 + p.Sq > (1 << 30)) refuse("0 <= q_pos0 and q_pos0 + Sq <= 2^30 required");
+  if (p.L < 1 || p.Sk % p.L) refuse("Sk must be a multiple of the segment length");
+  // kSelf takes Sk = Sq and q_pos0 = 0 as compile-time facts and reads neither from the arguments
+  if (p.self && (p.Sq != p.Sk || p.L != p.Sk || p.q_pos0 != 0))
+    refuse("self-attention needs Sq = Sk = seg_len and q_pos0 = 0");
 }
 
-void check_shape(int B, int64_t S, int Hq, int Hkv, int D) {
-  if (D != 64 && D != 128) throw std::invalid_argument("flash_attention: head dim must be 64 or 128");
-  if (B < 1 || B > 65535 || Hq < 1 || Hq > 65535) throw std::invalid_argument("flash_attention: 1 <= B, Hq <= 65535 required");
-  if (Hkv < 1 || Hq % Hkv) throw std::invalid_argument("flash_attention: Hq must be a multiple of Hkv");
-  if (S < 1 || S > (1 << 30)) throw std::invalid_argument("flash_attention: 1 <= S <= 2^30 required");
+// Checks a view and unpacks it into the kernel arguments.
+template <typename T>
+void take(const char* what, const View& v, T*& ptr, Strides& st, int64_t* seg = nullptr) {
+  const auto [p, sg, b, s, h] = v;
+  if (p == 0 || p % 16) refuse(std::string(what) + " must be 16-byte aligned");
+  if (b % 8 || s % 8 || h % 8) refuse(std::string(what) + " strides must be multiples of 8 elements");
+  if (sg % 8) refuse(std::string("segment stride of ") + what + " must be a multiple of 8 elements");
+  ptr = reinterpret_cast<T*>(p);
+  st = {b, s, h};
+  if (seg) *seg = sg;
 }
 
-// The chunk form's own rules: separate lengths, the position of query row 0 and the key segments.
-void check_chunk(int64_t Sq, int64_t Sk, int64_t L, int64_t q_pos0, int Hkv) {
-  if (Sk < 1 || Sk > (1 << 30)) throw std::invalid_argument("flash_attention_chunk: 1 <= Sk <= 2^30 required");
-  if (q_pos0 < 0 || q_pos0 + Sq > (1 << 30))
-    throw std::invalid_argument("flash_attention_chunk: 0 <= q_pos0 and q_pos0 + Sq <= 2^30 required");
-  if (L < 1 || Sk % L) throw std::invalid_argument("flash_attention_chunk: Sk must be a multiple of the segment length");
-  if (Hkv > 65535) throw std::invalid_argument("flash_attention_chunk: Hkv <= 65535 required");
+// The fields FwdArgs and BwdArgs share.
+template <typename Args>
+void fill(Args& a, const Problem& p, const View& q, const View& k, const View& v) {
+  check(p);
+  take("q", q, a.q, a.sq);
+  take("k", k, a.k, a.sk, &a.kseg);
+  take("v", v, a.v, a.sv, &a.vseg);
+  a.Sq = (int)p.Sq;
+  a.Sk = (int)p.Sk;
+  a.L = (int)p.L;
+  a.q_pos0 = (int)p.q_pos0;
+  a.Hq = p.Hq;
+  a.Hkv = p.Hkv;
+  a.scale_log2 = (float)(p.scale * 1.4426950408889634);
 }
 
-void check_seg(const char* what, int64_t seg) {
-  if (seg % 8) throw std::invalid_argument(std::string("flash_attention_chunk: segment stride of ") + what + " must be a multiple of 8 elements");
+// Calls f(D, causal, MODE) with the kernels' compile-time values as integral constants.  The mode
+// is the caller's: kSelf on its flag, else kChunk, or kSegmented when the key axis is segmented.
+template <typename F>
+void dispatch(const Problem& p, F&& f) {
+  auto by_mode = [&](auto d, auto c) {
+    if (p.self) f(d, c, std::integral_constant<int, kSelf>{});
+    else if (p.L == p.Sk) f(d, c, std::integral_constant<int, kChunk>{});
+    else f(d, c, std::integral_constant<int, kSegmented>{});
+  };
+  auto by_causal = [&](auto d) {
+    if (p.causal) by_mode(d, std::true_type{}); else by_mode(d, std::false_type{});
+  };
+  if (p.D == 64) by_causal(std::integral_constant<int, 64>{}); else by_causal(std::integral_constant<int, 128>{});
 }
 
-template <typename F64, typename F128>
-void by_dim(int D, F64&& f64, F128&& f128) {
-  if (D == 64) f64(); else f128();
-}
+dim3 query_grid(const Problem& p) { return dim3((unsigned)((p.Sq + kFlashBQ - 1) / kFlashBQ), (unsigned)p.Hq, (unsigned)p.B); }
 
-// One launcher per kernel: the self-attention entry points come here with Sq = Sk, q_pos0 = 0 and
-// L = Sk (kSelf), the chunk entry points with their own values (kChunk, or kSegmented when L < Sk).
-template <int MODE>
-void launch_fwd(const FwdArgs& a, int B, int D, bool causal, hipStream_t st) {
-  const dim3 grid((unsigned)((a.Sq + kFlashBQ - 1) / kFlashBQ), (unsigned)a.Hq, (unsigned)B), block(kFlashThreads);
-  auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, block, 0, st, a); };
-  if (causal) by_dim(D, [&] { go(k_flash_fwd<64, true, MODE>); }, [&] { go(k_flash_fwd<128, true, MODE>); });
-  else by_dim(D, [&] { go(k_flash_fwd<64, false, MODE>); }, [&] { go(k_flash_fwd<128, false, MODE>); });
-}
-
-template <int MODE>
-void launch_bwd(const BwdArgs& a, const uint16_t* outp, float* deltap, int B, int D, bool causal, hipStream_t st) {
-  const dim3 block(kFlashThreads);
-  const int64_t rows = (int64_t)B * a.Sq * a.Hq;
-  const int64_t dblocks = (rows + 16 * (kFlashThreads / 64) - 1) / (16 * (kFlashThreads / 64));
-  if (dblocks > 0x7fffffffLL) throw std::invalid_argument("flash_attention: B * S * Hq too large");
-  by_dim(D,
-         [&] { hipLaunchKernelGGL(k_flash_delta<64>, dim3((unsigned)dblocks), block, 0, st, a.dout, a.sdo, outp, deltap, rows, a.Sq, a.Hq); },
-         [&] { hipLaunchKernelGGL(k_flash_delta<128>, dim3((unsigned)dblocks), block, 0, st, a.dout, a.sdo, outp, deltap, rows, a.Sq, a.Hq); });
-
-  const dim3 gkv((unsigned)((a.Sk + kFlashBK - 1) / kFlashBK), (unsigned)a.Hkv, (unsigned)B);
-  auto gokv = [&](auto kern) { hipLaunchKernelGGL(kern, gkv, block, 0, st, a); };
-  if (causal) by_dim(D, [&] { gokv(k_flash_bwd_dkv<64, true, MODE>); }, [&] { gokv(k_flash_bwd_dkv<128, true, MODE>); });
-  else by_dim(D, [&] { gokv(k_flash_bwd_dkv<64, false, MODE>); }, [&] { gokv(k_flash_bwd_dkv<128, false, MODE>); });
-
-  const dim3 gq((unsigned)((a.Sq + kFlashBQ - 1) / kFlashBQ), (unsigned)a.Hq, (unsigned)B);
-  auto goq = [&](auto kern) { hipLaunchKernelGGL(kern, gq, block, 0, st, a); };
-  if (causal) by_dim(D, [&] { goq(k_flash_bwd_dq<64, true, MODE>); }, [&] { goq(k_flash_bwd_dq<128, true, MODE>); });
-  else by_dim(D, [&] { goq(k_flash_bwd_dq<64, false, MODE>); }, [&] { goq(k_flash_bwd_dq<128, false, MODE>); });
-}
-
-void fill_fwd(FwdArgs& a, uint64_t q, uint64_t k, uint64_t v, uint64_t out, uint64_t lse, int Hq, int Hkv, double scale) {
-  check_view("q", q, a.sq);
-  check_view("k", k, a.sk);
-  check_view("v", v, a.sv);
-  if (out == 0 || out % 16 || lse == 0 || lse % 4) throw std::invalid_argument("flash_attention: misaligned out / lse");
-  a.q = reinterpret_cast<const uint16_t*>(q);
-  a.k = reinterpret_cast<const uint16_t*>(k);
-  a.v = reinterpret_cast<const uint16_t*>(v);
+void flash_attn_fwd(const View& q, const View& k, const View& v, uint64_t out, uint64_t lse, int B, int64_t Sq, int64_t Sk,
+                    int64_t seg_len, int64_t q_pos0, int Hq, int Hkv, int D, bool causal, double scale, bool self_attention,
+                    uint64_t stream) {
+  const Problem p{B, Sq, Sk, seg_len, q_pos0, Hq, Hkv, D, causal, scale, self_attention};
+  FwdArgs a;
+  fill(a, p, q, k, v);
+  if (out == 0 || out % 16 || lse == 0 || lse % 4) refuse("misaligned out / lse");
   a.out = reinterpret_cast<uint16_t*>(out);
   a.lse = reinterpret_cast<float*>(lse);
-  a.Hq = Hq;
-  a.Hkv = Hkv;
-  a.scale_log2 = (float)(scale * 1.4426950408889634);
-}
-
-void fill_bwd(BwdArgs& a, uint64_t dout, uint64_t q, uint64_t k, uint64_t v, uint64_t out, uint64_t lse, uint64_t delta,
-              uint64_t dq, uint64_t dk, uint64_t dv, int Hq, int Hkv, double scale) {
-  check_view("q", q, a.sq);
-  check_view("k", k, a.sk);
-  check_view("v", v, a.sv);
-  check_view("dout", dout, a.sdo);
-  check_view("dk", dk, a.sdk);
-  check_view("dv", dv, a.sdv);
-  if (out == 0 || (out | dq | dk | dv) % 16 || dq == 0 || dk == 0 || dv == 0 || lse == 0 || delta == 0 || (lse | delta) % 4)
-    throw std::invalid_argument("flash_attention: misaligned out / lse / delta / dq / dk / dv");
-  a.q = reinterpret_cast<const uint16_t*>(q);
-  a.k = reinterpret_cast<const uint16_t*>(k);
-  a.v = reinterpret_cast<const uint16_t*>(v);
-  a.dout = reinterpret_cast<const uint16_t*>(dout);
-  a.lse = reinterpret_cast<const float*>(lse);
-  a.delta = reinterpret_cast<const float*>(delta);
-  a.dq = reinterpret_cast<uint16_t*>(dq);
-  a.dk = reinterpret_cast<uint16_t*>(dk);
-  a.dv = reinterpret_cast<uint16_t*>(dv);
-  a.Hq = Hq;
-  a.Hkv = Hkv;
-  a.scale = (float)scale;
-  a.scale_log2 = (float)(scale * 1.4426950408889634);
-}
-
-void flash_attn_fwd(uint64_t q, uint64_t k, uint64_t v, uint64_t out, uint64_t lse, int64_t q_sb, int64_t q_ss,
-                    int64_t q_sh, int64_t k_sb, int64_t k_ss, int64_t k_sh, int64_t v_sb, int64_t v_ss, int64_t v_sh, int B,
-                    int64_t S, int Hq, int Hkv, int D, bool causal, double scale, uint64_t stream) {
-  check_shape(B, S, Hq, Hkv, D);
-  FwdArgs a;
-  a.sq = {q_sb, q_ss, q_sh};
-  a.sk = {k_sb, k_ss, k_sh};
-  a.sv = {v_sb, v_ss, v_sh};
-  a.kseg = a.vseg = 0;
-  fill_fwd(a, q, k, v, out, lse, Hq, Hkv, scale);
-  a.Sq = a.Sk = a.L = (int)S;
-  a.q_pos0 = 0;
-  launch_fwd<kSelf>(a, B, D, causal, reinterpret_cast<hipStream_t>(stream));
-  CCMPI_HIP_CHECK(hipGetLastError());
-}
-
-void flash_attn_bwd(uint64_t dout, uint64_t q, uint64_t k, uint64_t v, uint64_t out, uint64_t lse, uint64_t delta,
-                    uint64_t dq, uint64_t dk, uint64_t dv, int64_t do_sb, int64_t do_ss, int64_t do_sh, int64_t q_sb,
-                    int64_t q_ss, int64_t q_sh, int64_t k_sb, int64_t k_ss, int64_t k_sh, int64_t v_sb, int64_t v_ss,
-                    int64_t v_sh, int B, int64_t S, int Hq, int Hkv, int D, bool causal, double scale, uint64_t stream) {
-  check_shape(B, S, Hq, Hkv, D);
-  BwdArgs a;
-  a.sq = {q_sb, q_ss, q_sh};
-  a.sk = {k_sb, k_ss, k_sh};
-  a.sv = {v_sb, v_ss, v_sh};
-  a.sdo = {do_sb, do_ss, do_sh};
-  a.sdk = a.sdv = {S * Hkv * D, (int64_t)Hkv * D, (int64_t)D};  // contiguous [B, S, Hkv, D]
-  a.kseg = a.vseg = a.dkseg = a.dvseg = 0;
-  fill_bwd(a, dout, q, k, v, out, lse, delta, dq, dk, dv, Hq, Hkv, scale);
-  a.Sq = a.Sk = a.L = (int)S;
-  a.q_pos0 = 0;
-  launch_bwd<kSelf>(a, reinterpret_cast<const uint16_t*>(out), reinterpret_cast<float*>(delta), B, D, causal,
-                    reinterpret_cast<hipStream_t>(stream));
-  CCMPI_HIP_CHECK(hipGetLastError());
-}
-
-// k / v strides come as (segment, batch, key, head); seg_len = Sk means one run (the segment
-// stride is then unused and the kChunk instantiations run).
-void flash_attn_chunk_fwd(uint64_t q, uint64_t k, uint64_t v, uint64_t out, uint64_t lse, int64_t q_sb, int64_t q_ss,
-                          int64_t q_sh, int64_t k_sg, int64_t k_sb, int64_t k_ss, int64_t k_sh, int64_t v_sg, int64_t v_sb,
-                          int64_t v_ss, int64_t v_sh, int B, int64_t Sq, int64_t Sk, int64_t seg_len, int64_t q_pos0, int Hq,
-                          int Hkv, int D, bool causal, double scale, uint64_t stream) {
-  check_shape(B, Sq, Hq, Hkv, D);
-  check_chunk(Sq, Sk, seg_len, q_pos0, Hkv);
-  FwdArgs a;
-  a.sq = {q_sb, q_ss, q_sh};
-  a.sk = {k_sb, k_ss, k_sh};
-  a.sv = {v_sb, v_ss, v_sh};
-  a.kseg = k_sg;
-  a.vseg = v_sg;
-  check_seg("k", k_sg);
-  check_seg("v", v_sg);
-  fill_fwd(a, q, k, v, out, lse, Hq, Hkv, scale);
-  a.Sq = (int)Sq;
-  a.Sk = (int)Sk;
-  a.L = (int)seg_len;
-  a.q_pos0 = (int)q_pos0;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (seg_len == Sk) launch_fwd<kChunk>(a, B, D, causal, st);
-  else launch_fwd<kSegmented>(a, B, D, causal, st);
+  dispatch(p, [&](auto d, auto c, auto m) {
+    hipLaunchKernelGGL((k_flash_fwd<decltype(d)::value, decltype(c)::value, decltype(m)::value>), query_grid(p),
+                       dim3(kFlashThreads), 0, st, a);
+  });
   CCMPI_HIP_CHECK(hipGetLastError());
 }
 
-void flash_attn_chunk_bwd(uint64_t dout, uint64_t q, uint64_t k, uint64_t v, uint64_t out, uint64_t lse, uint64_t delta,
-                          uint64_t dq, uint64_t dk, uint64_t dv, int64_t do_sb, int64_t do_ss, int64_t do_sh, int64_t q_sb,
-                          int64_t q_ss, int64_t q_sh, int64_t k_sg, int64_t k_sb, int64_t k_ss, int64_t k_sh, int64_t v_sg,
-                          int64_t v_sb, int64_t v_ss, int64_t v_sh, int64_t dk_sg, int64_t dk_sb, int64_t dk_ss,
-                          int64_t dk_sh, int64_t dv_sg, int64_t dv_sb, int64_t dv_ss, int64_t dv_sh, int B, int64_t Sq,
-                          int64_t Sk, int64_t seg_len, int64_t q_pos0, int Hq, int Hkv, int D, bool causal, double scale,
-                          uint64_t stream) {
-  check_shape(B, Sq, Hq, Hkv, D);
-  check_chunk(Sq, Sk, seg_len, q_pos0, Hkv);
+void flash_attn_bwd(const View& dout, const View& q, const View& k, const View& v, uint64_t out, uint64_t lse,
+                    uint64_t delta, uint64_t dq, const View& dk, const View& dv, int B, int64_t Sq, int64_t Sk,
+                    int64_t seg_len, int64_t q_pos0, int Hq, int Hkv, int D, bool causal, double scale, bool self_attention,
+                    uint64_t stream) {
+  const Problem p{B, Sq, Sk, seg_len, q_pos0, Hq, Hkv, D, causal, scale, self_attention};
   BwdArgs a;
-  a.sq = {q_sb, q_ss, q_sh};
-  a.sk = {k_sb, k_ss, k_sh};
-  a.sv = {v_sb, v_ss, v_sh};
-  a.sdo = {do_sb, do_ss, do_sh};
-  a.sdk = {dk_sb, dk_ss, dk_sh};
-  a.sdv = {dv_sb, dv_ss, dv_sh};
-  a.kseg = k_sg;
-  a.vseg = v_sg;
-  a.dkseg = dk_sg;
-  a.dvseg = dv_sg;
-  check_seg("k", k_sg);
-  check_seg("v", v_sg);
-  check_seg("dk", dk_sg);
-  check_seg("dv", dv_sg);
-  fill_bwd(a, dout, q, k, v, out, lse, delta, dq, dk, dv, Hq, Hkv, scale);
-  a.Sq = (int)Sq;
-  a.Sk = (int)Sk;
-  a.L = (int)seg_len;
-  a.q_pos0 = (int)q_pos0;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  fill(a, p, q, k, v);
+  if (Hkv > 65535) refuse("Hkv <= 65535 required");  // a grid dimension of the dK/dV kernel
+  take("dout", dout, a.dout, a.sdo);
+  take("dk", dk, a.dk, a.sdk, &a.dkseg);
+  take("dv", dv, a.dv, a.sdv, &a.dvseg);
+  if (self_attention) {
+    // the kSelf dK/dV store ignores the strides: they must be those of a contiguous [B, S, Hkv, D]
+    // tensor (0 stands for the stride of an axis of length 1)
+    const Strides want{Sk * Hkv * D, (int64_t)Hkv * D, (int64_t)D};
+    auto same = [](int64_t got, int64_t w, int64_t len) { return got == w || (len == 1 && got == 0); };
+    for (const Strides* s : {&a.sdk, &a.sdv})
+      if (!same(s->b, want.b, B) || !same(s->s, want.s, Sk) || !same(s->h, want.h, Hkv))
+        refuse("self-attention needs contiguous dk / dv");
+  }
+  if (out == 0 || (out | dq) % 16 || dq == 0 || lse == 0 || delta == 0 || (lse | delta) % 4)
+    refuse("misaligned out / lse / delta / dq");
+  const int64_t rows = (int64_t)B * Sq * Hq;
+  const int64_t dblocks = (rows + 16 * (kFlashThreads / 64) - 1) / (16 * (kFlashThreads / 64));
+  if (dblocks > 0x7fffffffLL) refuse("B * S * Hq too large");
   const uint16_t* outp = reinterpret_cast<const uint16_t*>(out);
   float* deltap = reinterpret_cast<float*>(delta);
-  if (seg_len == Sk) launch_bwd<kChunk>(a, outp, deltap, B, D, causal, st);
-  else launch_bwd<kSegmented>(a, outp, deltap, B, D, causal, st);
+  a.lse = reinterpret_cast<const float*>(lse);
+  a.delta = deltap;
+  a.dq = reinterpret_cast<uint16_t*>(dq);
+  a.scale = (float)scale;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const dim3 block(kFlashThreads), key_grid((unsigned)((Sk + kFlashBK - 1) / kFlashBK), (unsigned)Hkv, (unsigned)B);
+  dispatch(p, [&](auto d, auto c, auto m) {
+    constexpr int DD = decltype(d)::value, M = decltype(m)::value;
+    constexpr bool C = decltype(c)::value;
+    hipLaunchKernelGGL(k_flash_delta<DD>, dim3((unsigned)dblocks), block, 0, st, a.dout, a.sdo, outp, deltap, rows, a.Sq, a.Hq);
+    hipLaunchKernelGGL((k_flash_bwd_dkv<DD, C, M>), key_grid, block, 0, st, a);
+    hipLaunchKernelGGL((k_flash_bwd_dq<DD, C, M>), query_grid(p), block, 0, st, a);
+  });
   CCMPI_HIP_CHECK(hipGetLastError());
 }
 
@@ -743,39 +710,22 @@ void register_flash_attn_ops(pybind11::module_& m) {
   m.attr("FLASH_BQ") = kFlashBQ;
   m.attr("FLASH_BK") = kFlashBK;
   m.def("flash_attn_fwd", &flash_attn_fwd,
-        "self-attention forward: q [B, S, Hq, D], k / v [B, S, Hkv, D] bf16 views (element strides b, s, h; unit "
-        "stride on D) -> out [B, S, Hq, D] bf16 contiguous, lse [B, Hq, S] fp32",
-        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("out"), py::arg("lse"), py::arg("q_sb"), py::arg("q_ss"),
-        py::arg("q_sh"), py::arg("k_sb"), py::arg("k_ss"), py::arg("k_sh"), py::arg("v_sb"), py::arg("v_ss"),
-        py::arg("v_sh"), py::arg("B"), py::arg("S"), py::arg("Hq"), py::arg("Hkv"), py::arg("D"), py::arg("causal"),
-        py::arg("scale"), py::arg("stream"), py::call_guard<py::gil_scoped_release>());
-  m.def("flash_attn_bwd", &flash_attn_bwd,
-        "self-attention backward: delta [B, Hq, S] fp32 workspace, dq [B, S, Hq, D], dk / dv [B, S, Hkv, D] bf16 "
-        "contiguous; three launches (delta, dK/dV, dQ), no atomics",
-        py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("out"), py::arg("lse"), py::arg("delta"),
-        py::arg("dq"), py::arg("dk"), py::arg("dv"), py::arg("do_sb"), py::arg("do_ss"), py::arg("do_sh"),
-        py::arg("q_sb"), py::arg("q_ss"), py::arg("q_sh"), py::arg("k_sb"), py::arg("k_ss"), py::arg("k_sh"),
-        py::arg("v_sb"), py::arg("v_ss"), py::arg("v_sh"), py::arg("B"), py::arg("S"), py::arg("Hq"), py::arg("Hkv"),
-        py::arg("D"), py::arg("causal"), py::arg("scale"), py::arg("stream"), py::call_guard<py::gil_scoped_release>());
-  m.def("flash_attn_chunk_fwd", &flash_attn_chunk_fwd,
-        "chunk forward: q [B, Sq, Hq, D] at positions q_pos0.., k / v with Sk keys in segments of seg_len (element "
-        "strides segment, b, s, h); causal: key j visible to row i iff j <= q_pos0 + i -> out [B, Sq, Hq, D], lse [B, Hq, Sq]",
-        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("out"), py::arg("lse"), py::arg("q_sb"), py::arg("q_ss"),
-        py::arg("q_sh"), py::arg("k_sg"), py::arg("k_sb"), py::arg("k_ss"), py::arg("k_sh"), py::arg("v_sg"),
-        py::arg("v_sb"), py::arg("v_ss"), py::arg("v_sh"), py::arg("B"), py::arg("Sq"), py::arg("Sk"), py::arg("seg_len"),
-        py::arg("q_pos0"), py::arg("Hq"), py::arg("Hkv"), py::arg("D"), py::arg("causal"), py::arg("scale"),
-        py::arg("stream"), py::call_guard<py::gil_scoped_release>());
-  m.def("flash_attn_chunk_bwd", &flash_attn_chunk_bwd,
-        "chunk backward: dq [B, Sq, Hq, D] contiguous; dk / dv written through their own (segment, b, s, h) strides; a "
-        "key no query of the chunk sees gets exact zeros",
-        py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("out"), py::arg("lse"), py::arg("delta"),
-        py::arg("dq"), py::arg("dk"), py::arg("dv"), py::arg("do_sb"), py::arg("do_ss"), py::arg("do_sh"),
-        py::arg("q_sb"), py::arg("q_ss"), py::arg("q_sh"), py::arg("k_sg"), py::arg("k_sb"), py::arg("k_ss"),
-        py::arg("k_sh"), py::arg("v_sg"), py::arg("v_sb"), py::arg("v_ss"), py::arg("v_sh"), py::arg("dk_sg"),
-        py::arg("dk_sb"), py::arg("dk_ss"), py::arg("dk_sh"), py::arg("dv_sg"), py::arg("dv_sb"), py::arg("dv_ss"),
-        py::arg("dv_sh"), py::arg("B"), py::arg("Sq"), py::arg("Sk"), py::arg("seg_len"), py::arg("q_pos0"),
-        py::arg("Hq"), py::arg("Hkv"), py::arg("D"), py::arg("causal"), py::arg("scale"), py::arg("stream"),
+        "forward: q [B, Sq, Hq, D] at positions q_pos0.., k / v with Sk keys in segments of seg_len; each a bf16 view "
+        "(address, segment stride, b, s, h strides in elements; unit stride on D).  causal: key j visible to row i iff "
+        "j <= q_pos0 + i -> out [B, Sq, Hq, D] bf16 contiguous, lse [B, Hq, Sq] fp32.  self_attention: the "
+        "self-attention kernels (Sq = Sk = seg_len, q_pos0 = 0)",
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("out"), py::arg("lse"), py::arg("B"), py::arg("Sq"),
+        py::arg("Sk"), py::arg("seg_len"), py::arg("q_pos0"), py::arg("Hq"), py::arg("Hkv"), py::arg("D"),
+        py::arg("causal"), py::arg("scale"), py::arg("self_attention"), py::arg("stream"),
         py::call_guard<py::gil_scoped_release>());
+  m.def("flash_attn_bwd", &flash_attn_bwd,
+        "backward: delta [B, Hq, Sq] fp32 workspace, dq [B, Sq, Hq, D] bf16 contiguous; dk / dv views like k / v, "
+        "written through their own strides (a key no query sees gets exact zeros), contiguous [B, S, Hkv, D] with "
+        "self_attention; three launches (delta, dK/dV, dQ), no atomics",
+        py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("out"), py::arg("lse"), py::arg("delta"),
+        py::arg("dq"), py::arg("dk"), py::arg("dv"), py::arg("B"), py::arg("Sq"), py::arg("Sk"), py::arg("seg_len"),
+        py::arg("q_pos0"), py::arg("Hq"), py::arg("Hkv"), py::arg("D"), py::arg("causal"), py::arg("scale"),
+        py::arg("self_attention"), py::arg("stream"), py::call_guard<py::gil_scoped_release>());
 }
 
 }  // namespace dev

@@ -983,21 +983,95 @@ FLASH_HEAD_DIMS = (64, 128)
 _FLASH_MAX_GRID = 65535  # B and Hq are grid dimensions
 
 
-def _flash_view_check(name: str, t) -> None:
-    """The stride rules of a [B, S, H, D] operand read as a view: unit stride on D, every other
-    stride (of an axis longer than 1) a multiple of 8 elements, 16-byte-aligned base."""
-    if t.stride(3) != 1:
-        raise ValueError(f"flash_attention: {name} must have unit stride on the head dim, got strides {t.stride()}")
-    for ax in range(3):
-        if t.shape[ax] > 1 and t.stride(ax) % 8:
-            raise ValueError(f"flash_attention: stride {t.stride(ax)} of axis {ax} of {name} is not a multiple of 8 "
-                             "elements")
+_FLASH_MAX_POS = 1 << 30
+# The two public faces of the one implementation below: (name used in messages, self form).  The
+# self form is the chunk form with one length, q_pos0 = 0, no segments and contiguous dk / dv; it
+# runs the self-attention instantiations of the kernels.
+_FLASH_SELF = ("flash_attention", True)
+_FLASH_CHUNK = ("flash_attention_chunk", False)
+
+
+def flash_is_view(t) -> bool:
+    """Whether a [B, S, H, D] tensor can be read as it is (the stride rules of ``_flash_view_check``)."""
+    return (t.stride(3) == 1 and all(t.shape[ax] == 1 or t.stride(ax) % 8 == 0 for ax in range(3))
+            and t.data_ptr() % 16 == 0)
+
+
+def _flash_view_check(public: str, name: str, t) -> None:
+    """The stride rules of an operand read as a view, [B, S, H, D] or segmented [n, B, L, H, D]:
+    unit stride on D, every other stride (of an axis longer than 1) a multiple of 8 elements,
+    16-byte-aligned base."""
+    shape, stride = t.shape, t.stride()
+    if stride[-1] != 1:
+        raise ValueError(f"{public}: {name} must have unit stride on the head dim, got strides {stride}")
+    for ax in range(len(shape) - 1):
+        if shape[ax] > 1 and stride[ax] % 8:
+            what = f"the segment stride {stride[ax]}" if len(shape) == 5 and ax == 0 else f"stride {stride[ax]} of axis {ax}"
+            raise ValueError(f"{public}: {what} of {name} is not a multiple of 8 elements")
     if t.data_ptr() % 16:
-        raise ValueError(f"flash_attention: {name} must start at a 16-byte-aligned address")
+        raise ValueError(f"{public}: {name} must start at a 16-byte-aligned address")
 
 
-def _flash_strides(t):
-    return tuple(t.stride(ax) if t.shape[ax] > 1 else 0 for ax in range(3))
+def _flash_view(t):
+    """A view as the extension takes it: (address, segment, batch, row, head stride) in elements;
+    0 for an axis of length 1 and for the segment stride of a 4-D tensor."""
+    st = [s if n > 1 else 0 for n, s in zip(t.shape[:-1], t.stride())]
+    return (t.data_ptr(), *st) if len(st) == 4 else (t.data_ptr(), 0, *st)
+
+
+def _flash_validate(public: str, self_form: bool, q, k, v, q_pos0=0, kv_segment=None):
+    """The one rule list behind ``flash_attention_validate`` and ``flash_attention_chunk_validate``;
+    returns ``(B, Sq, Sk, L, Hq, Hkv, D)``.  The self form adds one rule: k and v have the length of q."""
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if t.dtype != torch.bfloat16:
+            raise TypeError(f"{public} expects bf16 {name}, got {t.dtype}")
+    if isinstance(q_pos0, bool) or not isinstance(q_pos0, int):
+        raise ValueError(f"{public}: q_pos0 must be an int, got {q_pos0!r}")
+    segmented = kv_segment is not None
+    if segmented and (isinstance(kv_segment, bool) or not isinstance(kv_segment, int) or kv_segment < 1):
+        raise ValueError(f"{public}: kv_segment must be None or a positive int, got {kv_segment!r}")
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if segmented and name != "q":
+            if t.dim() != 5:
+                raise ValueError(f"{public}: with kv_segment, {name} must be [n, B, L, Hkv, D], got {tuple(t.shape)}")
+        elif t.dim() != 4:
+            raise ValueError(f"{public}: {name} must be [B, S, H, D], got {tuple(t.shape)}")
+    B, Sq, Hq, D = q.shape
+    if segmented:
+        n, _, L, Hkv, _ = k.shape
+        want = (n, B, kv_segment, Hkv, D)
+        if L != kv_segment or tuple(k.shape) != want or tuple(v.shape) != want:
+            raise ValueError(f"{public}: k and v must both be [n, B = {B}, L = {kv_segment}, Hkv, D = {D}], "
+                             f"got {tuple(k.shape)} and {tuple(v.shape)}")
+        Sk = n * L
+    else:
+        _, Sk, Hkv, _ = k.shape
+        L = Sk
+        if tuple(k.shape) != (B, Sk, Hkv, D) or tuple(v.shape) != (B, Sk, Hkv, D):
+            raise ValueError(f"{public}: k and v must both be [B = {B}, Sk, Hkv, D = {D}], got "
+                             f"{tuple(k.shape)} and {tuple(v.shape)}")
+    if self_form and Sk != Sq:
+        raise ValueError(f"{public}: k and v must be [B = {B}, S = {Sq}, Hkv, D = {D}] like q, got "
+                         f"{tuple(k.shape)} and {tuple(v.shape)}")
+    if D not in FLASH_HEAD_DIMS:
+        raise ValueError(f"{public}: the head dim must be one of {FLASH_HEAD_DIMS}, got {D}")
+    if Sq < 1 or Sk < 1:
+        raise ValueError(f"{public}: q and k must have at least one position")
+    if Sk > _FLASH_MAX_POS:
+        raise ValueError(f"{public}: {'S' if self_form else 'Sk'} must be at most 2^30")
+    if q_pos0 < 0:
+        raise ValueError(f"{public}: q_pos0 must be >= 0 (key 0 is visible to every row), got {q_pos0}")
+    if q_pos0 + Sq > _FLASH_MAX_POS:
+        raise ValueError(f"{public}: q_pos0 + Sq must be at most 2^30")
+    if Hkv < 1 or Hq % Hkv:
+        raise ValueError(f"{public}: Hq = {Hq} must be a multiple of Hkv = {Hkv}")
+    if not (1 <= B <= _FLASH_MAX_GRID and Hq <= _FLASH_MAX_GRID):
+        raise ValueError(f"{public}: B and Hq must be in [1, {_FLASH_MAX_GRID}], got {B} and {Hq}")
+    if k.device != q.device or v.device != q.device:
+        raise ValueError(f"{public}: q, k and v must be on one device")
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        _flash_view_check(public, name, t)
+    return int(B), int(Sq), int(Sk), int(L), int(Hq), int(Hkv), int(D)
 
 
 def flash_attention_validate(q, k, v):
@@ -1006,32 +1080,22 @@ def flash_attention_validate(q, k, v):
     [B, S, Hq, D], ``k`` and ``v`` [B, S, Hkv, D], all bf16, taken as views: unit stride on D,
     batch / sequence / head strides multiples of 8 elements, 16-byte-aligned base.
     ``Hq % Hkv == 0``, ``D`` in {64, 128}, ``S >= 1``."""
-    for name, t in (("q", q), ("k", k), ("v", v)):
-        if t.dtype != torch.bfloat16:
-            raise TypeError(f"flash_attention expects bf16 {name}, got {t.dtype}")
-    for name, t in (("q", q), ("k", k), ("v", v)):
-        if t.dim() != 4:
-            raise ValueError(f"flash_attention: {name} must be [B, S, H, D], got {tuple(t.shape)}")
-    B, S, Hq, D = q.shape
-    Hkv = k.shape[2]
-    if tuple(k.shape) != (B, S, Hkv, D) or tuple(v.shape) != (B, S, Hkv, D):
-        raise ValueError(f"flash_attention: k and v must be [B = {B}, S = {S}, Hkv, D = {D}] like q, got "
-                         f"{tuple(k.shape)} and {tuple(v.shape)}")
-    if D not in FLASH_HEAD_DIMS:
-        raise ValueError(f"flash_attention: the head dim must be one of {FLASH_HEAD_DIMS}, got {D}")
-    if S < 1:
-        raise ValueError("flash_attention: the sequence must have at least one position")
-    if S > 1 << 30:
-        raise ValueError("flash_attention: S must be at most 2^30")
-    if Hkv < 1 or Hq % Hkv:
-        raise ValueError(f"flash_attention: Hq = {Hq} must be a multiple of Hkv = {Hkv}")
-    if not (1 <= B <= _FLASH_MAX_GRID and Hq <= _FLASH_MAX_GRID):
-        raise ValueError(f"flash_attention: B and Hq must be in [1, {_FLASH_MAX_GRID}], got {B} and {Hq}")
-    if k.device != q.device or v.device != q.device:
-        raise ValueError("flash_attention: q, k and v must be on one device")
-    for name, t in (("q", q), ("k", k), ("v", v)):
-        _flash_view_check(name, t)
-    return int(B), int(S), int(Hq), int(Hkv), int(D)
+    B, S, _, _, Hq, Hkv, D = _flash_validate(*_FLASH_SELF, q, k, v)
+    return B, S, Hq, Hkv, D
+
+
+def flash_attention_chunk_validate(q, k, v, q_pos0: int = 0, kv_segment: Optional[int] = None):
+    """Argument rules of ``flash_attention_chunk`` that need no GPU; raises TypeError (dtypes) /
+    ValueError (everything else) and returns ``(B, Sq, Sk, L, Hq, Hkv, D)``.
+
+    ``q`` is [B, Sq, Hq, D]: query row ``i`` sits at position ``q_pos0 + i`` of the key sequence
+    (``q_pos0 >= 0``, ``q_pos0 + Sq <= 2^30``).  ``kv_segment=None``: ``k`` and ``v`` are
+    [B, Sk, Hkv, D].  ``kv_segment=L``: they are 5-D views [n, B, L, Hkv, D] -- segment ``i`` holds
+    keys ``[i L, (i + 1) L)``, ``Sk = n L`` -- the rank-major layout an all-gather of per-rank
+    [B, L, Hkv, D] shards produces; the segment stride is ``k.stride(0)``.  All bf16 views: unit
+    stride on D, every other stride a multiple of 8 elements, 16-byte-aligned base.  ``Sq`` and
+    ``Sk`` are independent; ``1 <= Sk <= 2^30``."""
+    return _flash_validate(*_FLASH_CHUNK, q, k, v, q_pos0, kv_segment)
 
 
 def _flash_result(name: str, t, shape, dtype, like):
@@ -1047,11 +1111,91 @@ def _flash_result(name: str, t, shape, dtype, like):
     return t
 
 
+def _flash_kv_result(name: str, t, like_k):
+    """A caller's dk / dv of the chunk form: the shape of ``k`` (5-D on the segmented path), bf16,
+    on its device, under the view rules of ``k``; allocated contiguous when not given."""
+    if t is None:
+        return torch.empty(like_k.shape, dtype=torch.bfloat16, device=like_k.device)
+    if t.dtype != torch.bfloat16:
+        raise TypeError(f"flash_attention_chunk: {name} must be bf16, got {t.dtype}")
+    if tuple(t.shape) != tuple(like_k.shape) or t.device != like_k.device:
+        raise ValueError(f"flash_attention_chunk: {name} must be a {tuple(like_k.shape)} tensor on {like_k.device}, got "
+                         f"{tuple(t.shape)}")
+    _flash_view_check("flash_attention_chunk", name, t)
+    return t
+
+
 def _flash_scale(scale, D: int) -> float:
     s = D ** -0.5 if scale is None else float(scale)
     if not (s == s and abs(s) != float("inf")):
         raise ValueError("flash_attention: scale must be finite")
     return s
+
+
+def _flash_forward(public, self_form, q, k, v, causal, scale, out, lse, q_pos0=0, kv_segment=None):
+    B, Sq, Sk, L, Hq, Hkv, D = _flash_validate(public, self_form, q, k, v, q_pos0, kv_segment)
+    sc = _flash_scale(scale, D)
+    out = _flash_result("out", out, (B, Sq, Hq, D), torch.bfloat16, q)
+    lse = _flash_result("lse", lse, (B, Hq, Sq), torch.float32, q)
+    _D().flash_attn_fwd(_flash_view(q), _flash_view(k), _flash_view(v), out.data_ptr(), lse.data_ptr(), B, Sq, Sk, L,
+                        q_pos0, Hq, Hkv, D, bool(causal), sc, self_form, _stream(q))
+    return out, lse
+
+
+def _flash_backward(public, self_form, dout, q, k, v, out, lse, causal, scale, dq, dk, dv, delta, q_pos0=0,
+                    kv_segment=None):
+    B, Sq, Sk, L, Hq, Hkv, D = _flash_validate(public, self_form, q, k, v, q_pos0, kv_segment)
+    sc = _flash_scale(scale, D)
+    if dout.dtype != torch.bfloat16:
+        raise TypeError(f"{public} expects bf16 dout, got {dout.dtype}")
+    if tuple(dout.shape) != (B, Sq, Hq, D) or dout.device != q.device:
+        raise ValueError(f"{public}: dout must be {(B, Sq, Hq, D)} on {q.device}, got {tuple(dout.shape)}")
+    _flash_view_check(public, "dout", dout)
+    if out is None or lse is None:
+        raise ValueError(f"{public}_backward needs the forward's out and lse")
+    out = _flash_result("out", out, (B, Sq, Hq, D), torch.bfloat16, q)
+    lse = _flash_result("lse", lse, (B, Hq, Sq), torch.float32, q)
+
+    def result(name, t):
+        if name == "dq":
+            return _flash_result(name, t, (B, Sq, Hq, D), torch.bfloat16, q)
+        if name == "delta":
+            return _flash_result(name, t, (B, Hq, Sq), torch.float32, q)
+        # dk / dv: contiguous in the self form (its kernels ignore their strides), views like k in the chunk form
+        return _flash_result(name, t, k.shape, torch.bfloat16, q) if self_form else _flash_kv_result(name, t, k)
+
+    given = {"dq": dq, "dk": dk, "dv": dv, "delta": delta}
+    # every caller-provided result is checked before anything is allocated or launched; which
+    # error wins when two apply is each form's own order
+    for name in ("dq", "dk", "dv", "delta") if self_form else ("dk", "dv", "dq", "delta"):
+        if given[name] is not None:
+            result(name, given[name])
+    dq, dk, dv, delta = (result(name, t) for name, t in given.items())
+    _D().flash_attn_bwd(_flash_view(dout), _flash_view(q), _flash_view(k), _flash_view(v), out.data_ptr(),
+                        lse.data_ptr(), delta.data_ptr(), dq.data_ptr(), _flash_view(dk), _flash_view(dv), B, Sq, Sk, L,
+                        q_pos0, Hq, Hkv, D, bool(causal), sc, self_form, _stream(q))
+    return dq, dk, dv
+
+
+class _FlashAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, causal, scale, form, q_pos0, kv_segment):
+        out, lse = _flash_forward(*form, q, k, v, causal, scale, None, None, q_pos0, kv_segment)
+        ctx.save_for_backward(q, k, v, out, lse)
+        ctx.args = (form, causal, scale, q_pos0, kv_segment)
+        ctx.mark_non_differentiable(lse)
+        return out, lse
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout, _dlse):
+        q, k, v, out, lse = ctx.saved_tensors
+        form, causal, scale, q_pos0, kv_segment = ctx.args
+        if not flash_is_view(dout):  # e.g. an expanded or transposed gradient
+            dout = dout.contiguous()
+        dq, dk, dv = _flash_backward(*form, dout, q, k, v, out, lse, causal, scale, None, None, None, None, q_pos0,
+                                     kv_segment)
+        return dq, dk, dv, None, None, None, None, None
 
 
 def flash_attention_forward(q, k, v, causal: bool = True, scale: Optional[float] = None, out=None, lse=None):
@@ -1061,14 +1205,7 @@ def flash_attention_forward(q, k, v, causal: bool = True, scale: Optional[float]
     ``flash_attention_validate`` describes (views: no transposed copy); ``scale`` defaults to
     ``1 / sqrt(D)``.  Plain tensors, no autograd; no host synchronisation, and no allocation
     when ``out`` and ``lse`` are passed, so the call can be captured in a graph."""
-    B, S, Hq, Hkv, D = flash_attention_validate(q, k, v)
-    sc = _flash_scale(scale, D)
-    out = _flash_result("out", out, (B, S, Hq, D), torch.bfloat16, q)
-    lse = _flash_result("lse", lse, (B, Hq, S), torch.float32, q)
-    _D().flash_attn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr(),
-                        *_flash_strides(q), *_flash_strides(k), *_flash_strides(v), B, S, Hq, Hkv, D, bool(causal), sc,
-                        _stream(q))
-    return out, lse
+    return _flash_forward(*_FLASH_SELF, q, k, v, causal, scale, out, lse)
 
 
 def flash_attention_backward(dout, q, k, v, out, lse, causal: bool = True, scale: Optional[float] = None,
@@ -1080,50 +1217,7 @@ def flash_attention_backward(dout, q, k, v, out, lse, causal: bool = True, scale
     Three launches (delta, dK/dV, dQ): one workgroup owns each dK/dV key block and sums over its
     query heads and query blocks in a fixed order, one owns each dQ block, so there are no
     atomics and the gradients are bitwise reproducible."""
-    B, S, Hq, Hkv, D = flash_attention_validate(q, k, v)
-    sc = _flash_scale(scale, D)
-    if dout.dtype != torch.bfloat16:
-        raise TypeError(f"flash_attention expects bf16 dout, got {dout.dtype}")
-    if tuple(dout.shape) != (B, S, Hq, D) or dout.device != q.device:
-        raise ValueError(f"flash_attention: dout must be {(B, S, Hq, D)} on {q.device}, got {tuple(dout.shape)}")
-    _flash_view_check("dout", dout)
-    if out is None or lse is None:
-        raise ValueError("flash_attention_backward needs the forward's out and lse")
-    out = _flash_result("out", out, (B, S, Hq, D), torch.bfloat16, q)
-    lse = _flash_result("lse", lse, (B, Hq, S), torch.float32, q)
-    dq = _flash_result("dq", dq, (B, S, Hq, D), torch.bfloat16, q)
-    dk = _flash_result("dk", dk, (B, S, Hkv, D), torch.bfloat16, q)
-    dv = _flash_result("dv", dv, (B, S, Hkv, D), torch.bfloat16, q)
-    delta = _flash_result("delta", delta, (B, Hq, S), torch.float32, q)
-    _D().flash_attn_bwd(dout.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr(),
-                        delta.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), *_flash_strides(dout),
-                        *_flash_strides(q), *_flash_strides(k), *_flash_strides(v), B, S, Hq, Hkv, D, bool(causal), sc,
-                        _stream(q))
-    return dq, dk, dv
-
-
-def _flash_is_view(t) -> bool:
-    return (t.stride(3) == 1 and all(t.shape[ax] == 1 or t.stride(ax) % 8 == 0 for ax in range(3))
-            and t.data_ptr() % 16 == 0)
-
-
-class _FlashAttention(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, q, k, v, causal, scale):
-        out, lse = flash_attention_forward(q, k, v, causal, scale)
-        ctx.save_for_backward(q, k, v, out, lse)
-        ctx.causal, ctx.scale = causal, scale
-        ctx.mark_non_differentiable(lse)
-        return out, lse
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, dout, _dlse):
-        q, k, v, out, lse = ctx.saved_tensors
-        if not _flash_is_view(dout):  # e.g. an expanded or transposed gradient
-            dout = dout.contiguous()
-        dq, dk, dv = flash_attention_backward(dout, q, k, v, out, lse, ctx.causal, ctx.scale)
-        return dq, dk, dv, None, None
+    return _flash_backward(*_FLASH_SELF, dout, q, k, v, out, lse, causal, scale, dq, dk, dv, delta)
 
 
 def flash_attention(q, k, v, causal: bool = True, scale: Optional[float] = None):
@@ -1132,114 +1226,10 @@ def flash_attention(q, k, v, causal: bool = True, scale: Optional[float] = None)
     ``h // (Hq / Hkv)``), differentiable in all three.  Autograd keeps ``q``, ``k``, ``v``,
     ``out`` and ``lse``; nothing of size S x S exists."""
     flash_attention_validate(q, k, v)
-    return _FlashAttention.apply(q, k, v, bool(causal), scale)[0]
+    return _FlashAttention.apply(q, k, v, bool(causal), scale, _FLASH_SELF, 0, None)[0]
 
 
-# ---------------------------------------------------------------------------
-# chunk form: a query chunk at an offset into a longer, possibly segmented key sequence
-# ---------------------------------------------------------------------------
-_FLASH_MAX_POS = 1 << 30
-
-
-def _flash_kv_view_check(name: str, t, segmented: bool) -> None:
-    """Stride rules of a k / v / dk / dv operand of the chunk form: [B, Sk, Hkv, D], or segmented
-    [n, B, L, Hkv, D]; unit stride on D, every other stride (of an axis longer than 1) a multiple
-    of 8 elements, 16-byte-aligned base."""
-    nd = 5 if segmented else 4
-    if t.stride(nd - 1) != 1:
-        raise ValueError(f"flash_attention_chunk: {name} must have unit stride on the head dim, got strides {t.stride()}")
-    for ax in range(nd - 1):
-        if t.shape[ax] > 1 and t.stride(ax) % 8:
-            what = "the segment stride" if segmented and ax == 0 else f"stride of axis {ax}"
-            raise ValueError(f"flash_attention_chunk: {what} {t.stride(ax)} of {name} is not a multiple of 8 elements")
-    if t.data_ptr() % 16:
-        raise ValueError(f"flash_attention_chunk: {name} must start at a 16-byte-aligned address")
-
-
-def _flash_kv_strides(t, segmented: bool):
-    """(segment, batch, key, head) element strides; 0 for axes of length 1 and for no segments."""
-    st = tuple(t.stride(ax) if t.shape[ax] > 1 else 0 for ax in range(t.dim() - 1))
-    return st if segmented else (0,) + st
-
-
-def flash_attention_chunk_validate(q, k, v, q_pos0: int = 0, kv_segment: Optional[int] = None):
-    """Argument rules of ``flash_attention_chunk`` that need no GPU; raises TypeError (dtypes) /
-    ValueError (everything else) and returns ``(B, Sq, Sk, L, Hq, Hkv, D)``.
-
-    ``q`` is [B, Sq, Hq, D]: query row ``i`` sits at position ``q_pos0 + i`` of the key sequence
-    (``q_pos0 >= 0``, ``q_pos0 + Sq <= 2^30``).  ``kv_segment=None``: ``k`` and ``v`` are
-    [B, Sk, Hkv, D].  ``kv_segment=L``: they are 5-D views [n, B, L, Hkv, D] -- segment ``i`` holds
-    keys ``[i L, (i + 1) L)``, ``Sk = n L`` -- the rank-major layout an all-gather of per-rank
-    [B, L, Hkv, D] shards produces; the segment stride is ``k.stride(0)``.  All bf16 views: unit
-    stride on D, every other stride a multiple of 8 elements, 16-byte-aligned base.  ``Sq`` and
-    ``Sk`` are independent; ``1 <= Sk <= 2^30``."""
-    for name, t in (("q", q), ("k", k), ("v", v)):
-        if t.dtype != torch.bfloat16:
-            raise TypeError(f"flash_attention_chunk expects bf16 {name}, got {t.dtype}")
-    if isinstance(q_pos0, bool) or not isinstance(q_pos0, int):
-        raise ValueError(f"flash_attention_chunk: q_pos0 must be an int, got {q_pos0!r}")
-    segmented = kv_segment is not None
-    if segmented and (isinstance(kv_segment, bool) or not isinstance(kv_segment, int) or kv_segment < 1):
-        raise ValueError(f"flash_attention_chunk: kv_segment must be None or a positive int, got {kv_segment!r}")
-    if q.dim() != 4:
-        raise ValueError(f"flash_attention_chunk: q must be [B, Sq, Hq, D], got {tuple(q.shape)}")
-    B, Sq, Hq, D = q.shape
-    if segmented:
-        for name, t in (("k", k), ("v", v)):
-            if t.dim() != 5:
-                raise ValueError(f"flash_attention_chunk: with kv_segment, {name} must be [n, B, L, Hkv, D], got "
-                                 f"{tuple(t.shape)}")
-        n, _, L, Hkv, _ = k.shape
-        want = (n, B, kv_segment, Hkv, D)
-        if L != kv_segment or tuple(k.shape) != want or tuple(v.shape) != want:
-            raise ValueError(f"flash_attention_chunk: k and v must both be [n, B = {B}, L = {kv_segment}, Hkv, D = {D}], "
-                             f"got {tuple(k.shape)} and {tuple(v.shape)}")
-        Sk = n * L
-    else:
-        for name, t in (("k", k), ("v", v)):
-            if t.dim() != 4:
-                raise ValueError(f"flash_attention_chunk: {name} must be [B, Sk, Hkv, D], got {tuple(t.shape)}")
-        _, Sk, Hkv, _ = k.shape
-        L = Sk
-        if tuple(k.shape) != (B, Sk, Hkv, D) or tuple(v.shape) != (B, Sk, Hkv, D):
-            raise ValueError(f"flash_attention_chunk: k and v must both be [B = {B}, Sk, Hkv, D = {D}], got "
-                             f"{tuple(k.shape)} and {tuple(v.shape)}")
-    if D not in FLASH_HEAD_DIMS:
-        raise ValueError(f"flash_attention_chunk: the head dim must be one of {FLASH_HEAD_DIMS}, got {D}")
-    if Sq < 1 or Sk < 1:
-        raise ValueError("flash_attention_chunk: q and k must have at least one position")
-    if Sk > _FLASH_MAX_POS:
-        raise ValueError("flash_attention_chunk: Sk must be at most 2^30")
-    if q_pos0 < 0:
-        raise ValueError(f"flash_attention_chunk: q_pos0 must be >= 0 (key 0 is visible to every row), got {q_pos0}")
-    if q_pos0 + Sq > _FLASH_MAX_POS:
-        raise ValueError("flash_attention_chunk: q_pos0 + Sq must be at most 2^30")
-    if Hkv < 1 or Hq % Hkv:
-        raise ValueError(f"flash_attention_chunk: Hq = {Hq} must be a multiple of Hkv = {Hkv}")
-    if not (1 <= B <= _FLASH_MAX_GRID and Hq <= _FLASH_MAX_GRID):
-        raise ValueError(f"flash_attention_chunk: B and Hq must be in [1, {_FLASH_MAX_GRID}], got {B} and {Hq}")
-    if k.device != q.device or v.device != q.device:
-        raise ValueError("flash_attention_chunk: q, k and v must be on one device")
-    _flash_view_check("q", q)
-    _flash_kv_view_check("k", k, segmented)
-    _flash_kv_view_check("v", v, segmented)
-    return int(B), int(Sq), int(Sk), int(L), int(Hq), int(Hkv), int(D)
-
-
-def _flash_kv_result(name: str, t, like_k, segmented: bool):
-    """A caller's dk / dv of the chunk form: the shape of ``k`` (5-D on the segmented path), bf16,
-    on its device, under the view rules of ``k``; allocated contiguous when not given."""
-    if t is None:
-        return torch.empty(like_k.shape, dtype=torch.bfloat16, device=like_k.device)
-    if t.dtype != torch.bfloat16:
-        raise TypeError(f"flash_attention_chunk: {name} must be bf16, got {t.dtype}")
-    if tuple(t.shape) != tuple(like_k.shape) or t.device != like_k.device:
-        raise ValueError(f"flash_attention_chunk: {name} must be a {tuple(like_k.shape)} tensor on {like_k.device}, got "
-                         f"{tuple(t.shape)}")
-    _flash_kv_view_check(name, t, segmented)
-    return t
-
-
+# The chunk form: a query chunk at an offset into a longer, possibly segmented key sequence.
 def flash_attention_chunk_forward(q, k, v, causal: bool = True, scale: Optional[float] = None, out=None, lse=None, *,
                                   q_pos0: int = 0, kv_segment: Optional[int] = None):
     """``flash_attention_forward`` for a query chunk ``q`` [B, Sq, Hq, D] whose row 0 sits at
@@ -1249,15 +1239,7 @@ def flash_attention_chunk_forward(q, k, v, causal: bool = True, scale: Optional[
     bf16 contiguous, lse [B, Hq, Sq] fp32)``; for a chunk of a self-attention call these are bitwise
     the full call's rows.  No host synchronisation, and no allocation when ``out`` and ``lse`` are
     passed."""
-    B, Sq, Sk, L, Hq, Hkv, D = flash_attention_chunk_validate(q, k, v, q_pos0, kv_segment)
-    seg = kv_segment is not None
-    sc = _flash_scale(scale, D)
-    out = _flash_result("out", out, (B, Sq, Hq, D), torch.bfloat16, q)
-    lse = _flash_result("lse", lse, (B, Hq, Sq), torch.float32, q)
-    _D().flash_attn_chunk_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr(),
-                              *_flash_strides(q), *_flash_kv_strides(k, seg), *_flash_kv_strides(v, seg), B, Sq, Sk, L,
-                              q_pos0, Hq, Hkv, D, bool(causal), sc, _stream(q))
-    return out, lse
+    return _flash_forward(*_FLASH_CHUNK, q, k, v, causal, scale, out, lse, q_pos0, kv_segment)
 
 
 def flash_attention_chunk_backward(dout, q, k, v, out, lse, causal: bool = True, scale: Optional[float] = None,
@@ -1269,53 +1251,7 @@ def flash_attention_chunk_backward(dout, q, k, v, out, lse, causal: bool = True,
     buffer (the send buffer of a reduce-scatter); they hold this chunk's share only, and a key
     that no query of the chunk sees gets exact zeros.  ``delta`` [B, Hq, Sq] fp32 is the
     workspace.  With ``dq``, ``dk``, ``dv`` and ``delta`` passed the call allocates nothing."""
-    B, Sq, Sk, L, Hq, Hkv, D = flash_attention_chunk_validate(q, k, v, q_pos0, kv_segment)
-    seg = kv_segment is not None
-    sc = _flash_scale(scale, D)
-    if dout.dtype != torch.bfloat16:
-        raise TypeError(f"flash_attention_chunk expects bf16 dout, got {dout.dtype}")
-    if tuple(dout.shape) != (B, Sq, Hq, D) or dout.device != q.device:
-        raise ValueError(f"flash_attention_chunk: dout must be {(B, Sq, Hq, D)} on {q.device}, got {tuple(dout.shape)}")
-    _flash_view_check("dout", dout)
-    if out is None or lse is None:
-        raise ValueError("flash_attention_chunk_backward needs the forward's out and lse")
-    out = _flash_result("out", out, (B, Sq, Hq, D), torch.bfloat16, q)
-    lse = _flash_result("lse", lse, (B, Hq, Sq), torch.float32, q)
-    # every caller-provided result is checked before anything is allocated or launched
-    for name, t in (("dk", dk), ("dv", dv)):
-        if t is not None:
-            _flash_kv_result(name, t, k, seg)
-    dq = _flash_result("dq", dq, (B, Sq, Hq, D), torch.bfloat16, q)
-    delta = _flash_result("delta", delta, (B, Hq, Sq), torch.float32, q)
-    dk = _flash_kv_result("dk", dk, k, seg)
-    dv = _flash_kv_result("dv", dv, k, seg)
-    _D().flash_attn_chunk_bwd(dout.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr(),
-                              delta.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), *_flash_strides(dout),
-                              *_flash_strides(q), *_flash_kv_strides(k, seg), *_flash_kv_strides(v, seg),
-                              *_flash_kv_strides(dk, seg), *_flash_kv_strides(dv, seg), B, Sq, Sk, L, q_pos0, Hq, Hkv, D,
-                              bool(causal), sc, _stream(q))
-    return dq, dk, dv
-
-
-class _FlashAttentionChunk(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, q, k, v, causal, scale, q_pos0, kv_segment):
-        out, lse = flash_attention_chunk_forward(q, k, v, causal, scale, q_pos0=q_pos0, kv_segment=kv_segment)
-        ctx.save_for_backward(q, k, v, out, lse)
-        ctx.args = (causal, scale, q_pos0, kv_segment)
-        ctx.mark_non_differentiable(lse)
-        return out, lse
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, dout, _dlse):
-        q, k, v, out, lse = ctx.saved_tensors
-        causal, scale, q_pos0, kv_segment = ctx.args
-        if not _flash_is_view(dout):
-            dout = dout.contiguous()
-        dq, dk, dv = flash_attention_chunk_backward(dout, q, k, v, out, lse, causal, scale, q_pos0=q_pos0,
-                                                    kv_segment=kv_segment)
-        return dq, dk, dv, None, None, None, None
+    return _flash_backward(*_FLASH_CHUNK, dout, q, k, v, out, lse, causal, scale, dq, dk, dv, delta, q_pos0, kv_segment)
 
 
 def flash_attention_chunk(q, k, v, causal: bool = True, scale: Optional[float] = None, *, q_pos0: int = 0,
@@ -1324,4 +1260,4 @@ def flash_attention_chunk(q, k, v, causal: bool = True, scale: Optional[float] =
     in ``q``, ``k`` and ``v``; the gradients of ``k`` and ``v`` have their shape (5-D when
     segmented) and are this chunk's share."""
     flash_attention_chunk_validate(q, k, v, q_pos0, kv_segment)
-    return _FlashAttentionChunk.apply(q, k, v, bool(causal), scale, q_pos0, kv_segment)[0]
+    return _FlashAttention.apply(q, k, v, bool(causal), scale, _FLASH_CHUNK, q_pos0, kv_segment)[0]

@@ -29,11 +29,11 @@ from typing import Optional
 import torch
 
 from ..ops.kernels import (
-    _flash_is_view,
     flash_attention_chunk,
     flash_attention_chunk_backward,
     flash_attention_chunk_forward,
     flash_attention_chunk_validate,
+    flash_is_view,
 )
 from .layout import device_group_for
 
@@ -133,7 +133,7 @@ class _ContextParallelAttention(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, dout, _dlse):
         q, k, v, out, lse = ctx.saved_tensors
-        if not _flash_is_view(dout):
+        if not flash_is_view(dout):
             dout = dout.contiguous()
         dq, dk, dv = context_parallel_attention_backward(ctx.comm, dout, q, k, v, out, lse, ctx.causal, ctx.scale)
         return dq, dk, dv, None, None, None

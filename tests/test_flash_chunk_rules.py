@@ -7,6 +7,7 @@ import torch
 from collective_communication_mpi_amd import ops
 from collective_communication_mpi_amd.parallel import context_parallel_attention  # noqa: F401
 from collective_communication_mpi_amd.parallel.llama_dp import LlamaBlock, LlamaConfig
+import test_flash_attention_rules as self_rules
 
 B, SQ, SK, HQ, HKV, D = 2, 5, 12, 4, 2, 64
 BF = torch.bfloat16
@@ -148,6 +149,59 @@ def test_self_attention_still_refuses_another_key_length():
         ops.flash_attention_validate(_q(), _kv(), _kv())
     with pytest.raises(ValueError, match="flash_attention"):
         ops.flash_attention_validate(_q(), _segmented(1, SQ), _segmented(1, SQ))
+
+
+def _cases_of_both_forms():
+    """Every rejecting case of the two tables that both forms can express: q, k, v with
+    q_pos0 = 0 and kv_segment = None.  The self form has one sequence length, so a case of the
+    chunk table gets a q of its key length, and the self table's sequence_mismatch, which is
+    that one rule of its own, stays with test_self_attention_still_refuses_another_key_length."""
+    cases = [("self-" + make.__name__[5:], make(), error) for make, error in self_rules.RULES
+             if make is not self_rules._bad_sequence_mismatch]
+    for make, error in RULES:
+        (q, k, v, *offset), kw = make()
+        if offset or kw:
+            continue
+        if k.dim() == 4 and k.shape[1] != q.shape[1]:
+            q = torch.zeros(q.shape[0], k.shape[1], *q.shape[2:], dtype=q.dtype)
+        cases.append(("chunk-" + make.__name__[1:], (q, k, v), error))
+    return cases
+
+
+BOTH = _cases_of_both_forms()
+
+
+@pytest.mark.parametrize("qkv,error", [c[1:] for c in BOTH], ids=[c[0] for c in BOTH])
+def test_both_forms_refuse_alike(qkv, error):
+    """One rule list behind both validators: the same exception type, and messages that differ in
+    the prefix only."""
+    with pytest.raises(error) as as_self:
+        ops.flash_attention_validate(*qkv)
+    with pytest.raises(error) as as_chunk:
+        ops.flash_attention_chunk_validate(*qkv, q_pos0=0, kv_segment=None)
+    assert type(as_self.value) is type(as_chunk.value) is error
+    said, prefix = str(as_self.value), "flash_attention"
+    assert said.startswith(prefix) and not said.startswith(prefix + "_chunk")
+    assert str(as_chunk.value) == prefix + "_chunk" + said[len(prefix):]
+
+
+def test_both_tables_are_covered():
+    """Left to one form are only the cases it alone can express: an offset, segments, another key length."""
+    left_out = {"self-" + m.__name__[5:] for m, _ in self_rules.RULES} | {"chunk-" + m.__name__[1:] for m, _ in RULES}
+    left_out -= {c[0] for c in BOTH}
+    assert left_out == {"self-sequence_mismatch", "chunk-neg_offset", "chunk-offset_past_limit", "chunk-offset_not_int",
+                        "chunk-segment_shapes_differ", "chunk-segment_length_differs", "chunk-segment_stride_not_8",
+                        "chunk-segment_needs_5d"}
+
+
+def test_self_validator_returns_the_chunk_validators_dims():
+    fused = torch.zeros(B * SQ, (HQ + 2 * HKV) * D, dtype=BF)
+    sliced = (fused[:, :HQ * D].view(B, SQ, HQ, D), fused[:, HQ * D:(HQ + HKV) * D].view(B, SQ, HKV, D),
+              fused[:, (HQ + HKV) * D:].view(B, SQ, HKV, D))
+    for qkv in (self_rules._qkv(), self_rules._qkv(hq=8, hkv=1, d=128), self_rules._qkv(b=1, s=1, hq=1, hkv=1), sliced):
+        b, sq, sk, seg, hq, hkv, d = ops.flash_attention_chunk_validate(*qkv)
+        assert sq == sk == seg
+        assert ops.flash_attention_validate(*qkv) == (b, sq, hq, hkv, d)
 
 
 def test_model_refuses_context_parallel_sdpa():

@@ -14,7 +14,7 @@ import math
 import pytest
 import torch
 
-from collective_communication_mpi_amd import ops
+from collective_communication_mpi_amd import _native, ops
 from test_gpu_flash_attention import B, FLOOR, NAMES, _framed, _need_gpu  # noqa: F401  (_need_gpu: autouse skip)
 
 pytestmark = pytest.mark.gpu
@@ -182,6 +182,77 @@ def test_segmented_equals_flat_bitwise(n, L, Sq, p0, causal, Hq, Hkv, D):
     for name, buf, mask in (("dk", dkbuf, dkmask), ("dv", dvbuf, dvmask)):
         assert (buf[~mask] == -7.0).all(), f"the padding or the frame of {name} was overwritten"
         assert not torch.isnan(buf).any()
+
+
+def _padded(t, fill, pad=8, guard=64):
+    """``t`` [B, S, H, D] as an unsegmented view whose rows are ``pad`` elements further apart than
+    they are long, inside a buffer filled with ``fill``; returns (buffer, view, mask of the view)."""
+    _, S, H, D = t.shape
+    row = H * D + pad
+    buf = torch.full((2 * guard + B * S * row,), fill, dtype=t.dtype, device=t.device)
+    view = buf[guard:].as_strided((B, S, H, D), (S * row, row, D, 1))
+    mask = torch.zeros_like(buf, dtype=torch.bool)
+    mask[guard:].as_strided(view.shape, view.stride()).fill_(True)
+    view.copy_(t)
+    return buf, view, mask
+
+
+@pytest.mark.parametrize("Hq,Hkv,D", [(4, 2, 64), (8, 1, 128)])
+@pytest.mark.parametrize("causal", [True, False], ids=["causal", "full"])
+def test_strided_dk_dv_at_the_self_shape(causal, Hq, Hkv, D):
+    """Sq = Sk and q_pos0 = 0 through the chunk call stay a chunk call: dk / dv go through their
+    strides.  70 keys are two key blocks, the second ragged."""
+    S = 70
+    q, k, v, dout = _inputs(S, S, Hq, Hkv, D, salt=6)
+    out, lse = ops.flash_attention_forward(q, k, v, causal)
+    want = (out, lse, *ops.flash_attention_backward(dout, q, k, v, out, lse, causal))
+    nan = float("nan")
+    _, ks, _ = _padded(k, nan)
+    _, vs, _ = _padded(v, nan, pad=16)
+    dkbuf, dks, dkmask = _padded(torch.full_like(k, -7.0), -7.0, pad=16)
+    dvbuf, dvs, dvmask = _padded(torch.full_like(v, -7.0), -7.0)
+    assert not ks.is_contiguous() and not dks.is_contiguous() and ks.stride(1) != dks.stride(1)
+    got = _run(q, ks, vs, dout, causal, 0, dk=dks, dv=dvs)
+    assert got[3].data_ptr() == dks.data_ptr() and got[4].data_ptr() == dvs.data_ptr()
+    for name, g, w in zip(("out", "lse", "dq", "dk", "dv"), got, want):
+        assert torch.equal(g, w), f"{name} differs from self-attention on contiguous copies"
+    for name, buf, mask in (("dk", dkbuf, dkmask), ("dv", dvbuf, dvmask)):
+        assert (buf[~mask] == -7.0).all(), f"the padding or the frame of {name} was overwritten"
+        assert not torch.isnan(buf).any()
+
+
+def test_self_attention_flag_is_guarded():
+    """The extension refuses, before any launch, a self_attention call whose arguments are not
+    those of self-attention: the kSelf kernels read neither Sk nor q_pos0 nor the dk / dv strides."""
+    S, D = 16, 64
+    dev = _native.device()
+    stream = torch.cuda.current_stream().cuda_stream
+    q, k, v, dout = (torch.zeros(1, S, 1, D, dtype=torch.bfloat16, device="cuda") for _ in range(4))
+    fr = {"out": _framed((1, S, 1, D), torch.bfloat16, -7.0), "lse": _framed((1, 1, S), torch.float32, -7.0),
+          "dq": _framed((1, S, 1, D), torch.bfloat16, -7.0), "delta": _framed((1, 1, S), torch.float32, -7.0),
+          "dk": _framed((1, S, 1, D + 8), torch.bfloat16, -7.0), "dv": _framed((1, S, 1, D), torch.bfloat16, -7.0)}
+    o = {name: view for name, (_, view) in fr.items()}
+    view = lambda t, row=D: (t.data_ptr(), 0, 0, row, 0)  # B = Hkv = 1: stride 0 on their axes
+    ptr = lambda name: o[name].data_ptr()
+
+    def fwd(Sq=S, Sk=S, seg_len=S, q_pos0=0):
+        dev.flash_attn_fwd(view(q), view(k), view(v), ptr("out"), ptr("lse"), 1, Sq, Sk, seg_len, q_pos0, 1, 1, D, True,
+                           D ** -0.5, True, stream)
+
+    def bwd(Sq=S, Sk=S, seg_len=S, q_pos0=0, dk_row=D):
+        dev.flash_attn_bwd(view(dout), view(q), view(k), view(v), ptr("out"), ptr("lse"), ptr("delta"), ptr("dq"),
+                           view(o["dk"], dk_row), view(o["dv"]), 1, Sq, Sk, seg_len, q_pos0, 1, 1, D, True, D ** -0.5, True,
+                           stream)
+
+    for call in (fwd, bwd):
+        for bad in (dict(Sq=8), dict(Sk=8, seg_len=8), dict(q_pos0=8), dict(seg_len=8)):
+            with pytest.raises(ValueError, match="self-attention"):
+                call(**bad)
+    with pytest.raises(ValueError, match="contiguous dk / dv"):
+        bwd(dk_row=D + 8)
+    torch.cuda.synchronize()
+    for name, (buf, _) in fr.items():
+        assert (buf == -7.0).all(), f"a refused call wrote {name}"
 
 
 def test_graph_replay_equals_eager():
