@@ -53,6 +53,21 @@
 // instantiation runs is the caller's choice (the self_attention flag of the two entry points), not
 // a property of the values: a chunk call with Sq = Sk and q_pos0 = 0 still runs kChunk.
 //
+// PACKED form (ops.flash_attention_varlen, kVarlen): q [T, Hq, D], k / v [T, Hkv, D] hold n sequences
+// back to back, sequence i on rows [cu[i], cu[i + 1]) of all three; cu [n + 1] int32 is read ON THE
+// DEVICE, so the host knows T and n alone (no synchronisation, capturable, and a replayed graph
+// follows the contents of cu).  Inside a sequence it is self-attention (Sq = Sk = its length,
+// q_pos0 = 0); no key of another sequence is visible.  The grid has T / BLK + n slots (BLK rows or
+// keys per workgroup); sequence i owns those from cu[i] / BLK + i on, which never overlap since
+// cu[i + 1] / BLK + 1 >= cu[i] / BLK + ceil(len_i / BLK).  A workgroup finds the sequence of its slot
+// by bisection over cu (uniform loads, no LDS) and leaves before its first barrier when the slot
+// is spare.  Tiles therefore start at the sequence's first row: the sums run over the same key and
+// query steps in the same order as a self-attention call on that sequence alone, and out, lse, dq,
+// dk and dv rows are bitwise that call's.  Boundaries are clamped (begin into [0, T], end into
+// [begin, T]) so no content of cu makes any address leave the tensors; cu[n] > T truncates the
+// last sequence, rows from cu[n] on are never written, anything else unpromised gives unspecified
+// values.
+//
 // P is recomputed in both backward kernels (seven products per tile pair instead of five): no
 // atomics, no hand-off between workgroups, every sum has one owner and a fixed order, so all
 // five outputs are bitwise reproducible.  Only plain vector stores write global memory.
@@ -92,8 +107,11 @@ struct FwdArgs {
   int Sq, Hq, Hkv;
   float scale_log2;
   // the chunk form's own arguments follow those of self-attention, whose layout is unchanged
-  int Sk, q_pos0, L;
-  int64_t kseg, vseg;  // segment strides of k / v (kSegmented only)
+  // kVarlen reads none of them: there Sq is T and two slots carry the packing instead
+  int Sk, q_pos0;
+  union { int L; int n; };                 // kSegmented: keys per segment; kVarlen: sequences
+  union { int64_t kseg; const int* cu; };  // kSegmented: segment stride of k; kVarlen: boundaries [n + 1]
+  int64_t vseg;                            // segment stride of v (kSegmented only)
 };
 
 struct BwdArgs {
@@ -104,16 +122,42 @@ struct BwdArgs {
   int Sq, Hq, Hkv;
   float scale, scale_log2;
   // the chunk form's own arguments follow those of self-attention, whose layout is unchanged
-  int Sk, q_pos0, L;
+  // kVarlen reads none of them: there Sq is T and two slots carry the packing instead
+  int Sk, q_pos0;
+  union { int L; int n; };  // kSegmented: keys per segment; kVarlen: sequences
   Strides sdk, sdv;
-  int64_t kseg, vseg, dkseg, dvseg;  // segment strides of k / v / dk / dv (kSegmented only)
+  union { int64_t kseg; const int* cu; };  // kSegmented: segment stride of k; kVarlen: boundaries [n + 1]
+  int64_t vseg, dkseg, dvseg;              // segment strides of v / dk / dv (kSegmented only)
 };
 
 // Instantiations of every kernel.  kSelf is self-attention as it always was: one length (Sk = Sq),
 // q_pos0 = 0 and contiguous dk / dv are compile-time facts there, so it keeps its code and its
 // speed; kChunk reads Sq, Sk and q_pos0 from the arguments and writes dk / dv through their
-// strides; kSegmented adds the segmented key axis.
-constexpr int kSelf = 0, kChunk = 1, kSegmented = 2;
+// strides; kSegmented adds the segmented key axis; kVarlen is self-attention inside each sequence
+// of a packed token axis, the boundaries read from cu.
+constexpr int kSelf = 0, kChunk = 1, kSegmented = 2, kVarlen = 3;
+
+// kVarlen: where the workgroup of one slot works.  Sequence i owns rows [begin, begin + len) of the
+// token axis, begin = clamp(cu[i], 0, T) and the end clamped into [begin, T], and the slots from
+// begin / BLK + i on: the slot's sequence is the last one that starts at or before it (bisection,
+// uniform loads), `tile` its BLK-row block inside that sequence.  The slot is spare when the tile
+// lies past the sequence (or before it, which only a broken cu produces).
+struct Slot {
+  int begin, len, tile;
+  template <int BLK>
+  __device__ __forceinline__ bool spare() const { return tile < 0 || tile * BLK >= len; }
+};
+template <int BLK>
+__device__ __forceinline__ Slot varlen_slot(const int* cu, int n, int T, int slot) {
+  auto at = [&](int i) { return min(max(cu[i], 0), T); };
+  int lo = 0, hi = n;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (at(mid) / BLK + mid <= slot) lo = mid; else hi = mid;
+  }
+  const int begin = at(lo), end = max(at(lo + 1), begin);
+  return {begin, end - begin, slot - (begin / BLK + lo)};
+}
 
 // Element offset of key row `key` on the key axis of k / v / dk / dv.  SEG: the axis is cut into
 // segments of L keys, `seg` elements apart (the rank-major layout of an all-gather); otherwise
@@ -133,6 +177,8 @@ struct Mask {
   int Sq, Sk, p0;
   template <typename Args>
   __device__ __forceinline__ explicit Mask(const Args& a) : Sq(a.Sq), Sk(MODE ? a.Sk : a.Sq), p0(MODE ? a.q_pos0 : 0) {}
+  // kVarlen: self-attention inside one sequence of the packing
+  __device__ __forceinline__ explicit Mask(int len) : Sq(len), Sk(len), p0(0) {}
   // key lies above the diagonal of row qi + d
   __device__ __forceinline__ bool above(int qi, int key, int d = 0) const { return CAUSAL && key > p0 + qi + d; }
   // rows past Sq are computed and never stored, so the forward leaves the row test out
@@ -192,14 +238,20 @@ __global__ __launch_bounds__(kFlashThreads) void k_flash_fwd(const FwdArgs a) {
   __shared__ __attribute__((aligned(16))) uint16_t Ks[kFlashBK * LDK];
   __shared__ __attribute__((aligned(16))) uint16_t Vt[D * LDT];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c = lane & 15, g = lane >> 4;
-  const int qb = (int)(gridDim.x - 1 - blockIdx.x), h = blockIdx.y, b = blockIdx.z;  // heaviest blocks first
-  constexpr bool SEG = MODE == kSegmented;
-  const Mask<CAUSAL, MODE> mask(a);
+  const int h = blockIdx.y, b = blockIdx.z;
+  constexpr bool SEG = MODE == kSegmented, VAR = MODE == kVarlen;
+  Slot sl{0, 0, (int)(gridDim.x - 1 - blockIdx.x)};  // heaviest blocks first
+  if constexpr (VAR) {
+    sl = varlen_slot<kFlashBQ>(a.cu, a.n, a.Sq, sl.tile);
+    if (sl.template spare<kFlashBQ>()) return;
+  }
+  const int qb = sl.tile;
+  const Mask<CAUSAL, MODE> mask = VAR ? Mask<CAUSAL, MODE>(sl.len) : Mask<CAUSAL, MODE>(a);
   const int hk = h / (a.Hq / a.Hkv), Sq = mask.Sq, Sk = mask.Sk;
   const int q0 = qb * kFlashBQ, qw = q0 + wave * (16 * kFlashQT);
-  const uint16_t* qp = a.q + b * a.sq.b + h * a.sq.h;
-  const uint16_t* kp = a.k + b * a.sk.b + hk * a.sk.h;
-  const uint16_t* vp = a.v + b * a.sv.b + hk * a.sv.h;
+  const uint16_t* qp = a.q + b * a.sq.b + h * a.sq.h + sl.begin * a.sq.s;
+  const uint16_t* kp = a.k + b * a.sk.b + hk * a.sk.h + sl.begin * a.sk.s;
+  const uint16_t* vp = a.v + b * a.sv.b + hk * a.sv.h + sl.begin * a.sv.s;
 
   bf16x8 qf[kFlashQT][KK];
 #pragma unroll
@@ -318,10 +370,12 @@ __global__ __launch_bounds__(kFlashThreads) void k_flash_fwd(const FwdArgs a) {
     lt += __shfl_xor(lt, 32);
     if (qi >= Sq) continue;
     const float inv = 1.0f / lt;
-    uint16_t* op = a.out + (((int64_t)b * Sq + qi) * a.Hq + h) * D + 4 * g;
+    // kVarlen: out [T, Hq, D] and lse [Hq, T] at the sequence's first row
+    uint16_t* op = a.out + (((VAR ? (int64_t)sl.begin : (int64_t)b * Sq) + qi) * a.Hq + h) * D + 4 * g;
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) st_g8(op + 16 * dt, o[t][dt], inv);
-    if (g == 0) a.lse[((int64_t)b * a.Hq + h) * Sq + qi] = (m[t] + __log2f(lt)) * kLn2;
+    if (g == 0)
+      a.lse[(VAR ? (int64_t)h * a.Sq + sl.begin : ((int64_t)b * a.Hq + h) * Sq) + qi] = (m[t] + __log2f(lt)) * kLn2;
   }
 }
 
@@ -359,13 +413,19 @@ __global__ __launch_bounds__(kFlashThreads) void k_flash_bwd_dkv(const BwdArgs a
   __shared__ __attribute__((aligned(16))) float Ls[kFlashBwdQ];
   __shared__ __attribute__((aligned(16))) float Ds[kFlashBwdQ];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c = lane & 15, g = lane >> 4;
-  const int kb = blockIdx.x, hk = blockIdx.y, b = blockIdx.z;
-  constexpr bool SEG = MODE == kSegmented;
-  const Mask<CAUSAL, MODE> mask(a);
+  const int hk = blockIdx.y, b = blockIdx.z;
+  constexpr bool SEG = MODE == kSegmented, VAR = MODE == kVarlen;
+  Slot sl{0, 0, (int)blockIdx.x};
+  if constexpr (VAR) {
+    sl = varlen_slot<kFlashBK>(a.cu, a.n, a.Sq, sl.tile);
+    if (sl.template spare<kFlashBK>()) return;
+  }
+  const int kb = sl.tile;
+  const Mask<CAUSAL, MODE> mask = VAR ? Mask<CAUSAL, MODE>(sl.len) : Mask<CAUSAL, MODE>(a);
   const int Sq = mask.Sq, Sk = mask.Sk, rep = a.Hq / a.Hkv;
   const int key0 = kb * kFlashBK, kw = key0 + 16 * wave, keyi = kw + c;
-  const uint16_t* kp = a.k + b * a.sk.b + hk * a.sk.h + key_off<SEG>(keyi, a.L, a.kseg, a.sk.s);
-  const uint16_t* vp = a.v + b * a.sv.b + hk * a.sv.h + key_off<SEG>(keyi, a.L, a.vseg, a.sv.s);
+  const uint16_t* kp = a.k + b * a.sk.b + hk * a.sk.h + sl.begin * a.sk.s + key_off<SEG>(keyi, a.L, a.kseg, a.sk.s);
+  const uint16_t* vp = a.v + b * a.sv.b + hk * a.sv.h + sl.begin * a.sv.s + key_off<SEG>(keyi, a.L, a.vseg, a.sv.s);
   bf16x8 kf[KK], vf[KK];
 #pragma unroll
   for (int kk = 0; kk < KK; ++kk) {
@@ -387,15 +447,15 @@ __global__ __launch_bounds__(kFlashThreads) void k_flash_bwd_dkv(const BwdArgs a
   auto fetch = [&](int i) {
     const int h = hk * rep + i / nq, qi = (qs0 + i % nq) * kFlashBwdQ + row;
     const bool ok = qi < Sq;
-    const uint16_t* qp = a.q + b * a.sq.b + h * a.sq.h + (int64_t)qi * a.sq.s;
-    const uint16_t* dp = a.dout + b * a.sdo.b + h * a.sdo.h + (int64_t)qi * a.sdo.s;
+    const uint16_t* qp = a.q + b * a.sq.b + h * a.sq.h + ((int64_t)sl.begin + qi) * a.sq.s;
+    const uint16_t* dp = a.dout + b * a.sdo.b + h * a.sdo.h + ((int64_t)sl.begin + qi) * a.sdo.s;
 #pragma unroll
     for (int j = 0; j < NP; ++j) {
       qr[j] = ld_g16(qp + (cb + 8 * j) * 8, ok);
       dr[j] = ld_g16(dp + (cb + 8 * j) * 8, ok);
     }
     if (tid < kFlashBwdQ) {
-      const int64_t o = ((int64_t)b * a.Hq + h) * Sq + qi;
+      const int64_t o = (VAR ? (int64_t)h * a.Sq + sl.begin : ((int64_t)b * a.Hq + h) * Sq) + qi;
       lv = ok ? a.lse[o] * kLog2e : 0.f;
       dl = ok ? a.delta[o] : 0.f;
     }
@@ -447,10 +507,11 @@ __global__ __launch_bounds__(kFlashThreads) void k_flash_bwd_dkv(const BwdArgs a
     }
   }
   if (keyi < Sk) {
-    // self-attention: dk / dv are contiguous [B, S, Hkv, D]
-    const int64_t o = MODE ? 0 : (((int64_t)b * Sk + keyi) * a.Hkv + hk) * D;
-    uint16_t* dkp = a.dk + (MODE ? b * a.sdk.b + hk * a.sdk.h + key_off<SEG>(keyi, a.L, a.dkseg, a.sdk.s) : o) + 4 * g;
-    uint16_t* dvp = a.dv + (MODE ? b * a.sdv.b + hk * a.sdv.h + key_off<SEG>(keyi, a.L, a.dvseg, a.sdv.s) : o) + 4 * g;
+    // self-attention: dk / dv are contiguous [B, S, Hkv, D]; kVarlen: contiguous [T, Hkv, D]
+    constexpr bool DENSE = MODE == kSelf || VAR;
+    const int64_t o = DENSE ? (((VAR ? (int64_t)sl.begin : (int64_t)b * Sk) + keyi) * a.Hkv + hk) * D : 0;
+    uint16_t* dkp = a.dk + (DENSE ? o : b * a.sdk.b + hk * a.sdk.h + key_off<SEG>(keyi, a.L, a.dkseg, a.sdk.s)) + 4 * g;
+    uint16_t* dvp = a.dv + (DENSE ? o : b * a.sdv.b + hk * a.sdv.h + key_off<SEG>(keyi, a.L, a.dvseg, a.sdv.s)) + 4 * g;
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) {
       st_g8(dkp + 16 * dt, dk[dt], a.scale);
@@ -466,15 +527,21 @@ __global__ __launch_bounds__(kFlashThreads) void k_flash_bwd_dq(const BwdArgs a)
   __shared__ __attribute__((aligned(16))) uint16_t Vs[kFlashBK * LDK];
   __shared__ __attribute__((aligned(16))) uint16_t Kt[D * LDT];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c = lane & 15, g = lane >> 4;
-  const int qb = (int)(gridDim.x - 1 - blockIdx.x), h = blockIdx.y, b = blockIdx.z;
-  constexpr bool SEG = MODE == kSegmented;
-  const Mask<CAUSAL, MODE> mask(a);
+  const int h = blockIdx.y, b = blockIdx.z;
+  constexpr bool SEG = MODE == kSegmented, VAR = MODE == kVarlen;
+  Slot sl{0, 0, (int)(gridDim.x - 1 - blockIdx.x)};
+  if constexpr (VAR) {
+    sl = varlen_slot<kFlashBQ>(a.cu, a.n, a.Sq, sl.tile);
+    if (sl.template spare<kFlashBQ>()) return;
+  }
+  const int qb = sl.tile;
+  const Mask<CAUSAL, MODE> mask = VAR ? Mask<CAUSAL, MODE>(sl.len) : Mask<CAUSAL, MODE>(a);
   const int hk = h / (a.Hq / a.Hkv), Sq = mask.Sq, Sk = mask.Sk;
   const int q0 = qb * kFlashBQ, qw = q0 + wave * (16 * kFlashQT);
-  const uint16_t* qp = a.q + b * a.sq.b + h * a.sq.h;
-  const uint16_t* dop = a.dout + b * a.sdo.b + h * a.sdo.h;
-  const uint16_t* kp = a.k + b * a.sk.b + hk * a.sk.h;
-  const uint16_t* vp = a.v + b * a.sv.b + hk * a.sv.h;
+  const uint16_t* qp = a.q + b * a.sq.b + h * a.sq.h + sl.begin * a.sq.s;
+  const uint16_t* dop = a.dout + b * a.sdo.b + h * a.sdo.h + sl.begin * a.sdo.s;
+  const uint16_t* kp = a.k + b * a.sk.b + hk * a.sk.h + sl.begin * a.sk.s;
+  const uint16_t* vp = a.v + b * a.sv.b + hk * a.sv.h + sl.begin * a.sv.s;
 
   bf16x8 qf[kFlashQT][KK], dof[kFlashQT][KK];
   float lse2[kFlashQT], dl[kFlashQT];
@@ -488,7 +555,7 @@ __global__ __launch_bounds__(kFlashThreads) void k_flash_bwd_dq(const BwdArgs a)
       qf[t][kk] = ld_query_frag(qp, a.sq.s, qi, kk, g, ok);
       dof[t][kk] = ld_query_frag(dop, a.sdo.s, qi, kk, g, ok);
     }
-    const int64_t o = ((int64_t)b * a.Hq + h) * Sq + qi;
+    const int64_t o = (VAR ? (int64_t)h * a.Sq + sl.begin : ((int64_t)b * a.Hq + h) * Sq) + qi;
     lse2[t] = ok ? a.lse[o] * kLog2e : 0.f;
     dl[t] = ok ? a.delta[o] : 0.f;
 #pragma unroll
@@ -565,7 +632,7 @@ __global__ __launch_bounds__(kFlashThreads) void k_flash_bwd_dq(const BwdArgs a)
   for (int t = 0; t < kFlashQT; ++t) {
     const int qi = qw + 16 * t + c;
     if (qi >= Sq) continue;
-    uint16_t* op = a.dq + (((int64_t)b * Sq + qi) * a.Hq + h) * D + 4 * g;
+    uint16_t* op = a.dq + (((VAR ? (int64_t)sl.begin : (int64_t)b * Sq) + qi) * a.Hq + h) * D + 4 * g;
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) st_g8(op + 16 * dt, dq[t][dt], a.scale);
   }
@@ -582,7 +649,13 @@ struct Problem {
   bool causal;
   double scale;
   bool self;  // the caller's flag: run kSelf
+  // the packed form (run kVarlen): the device address of the n + 1 boundaries, else 0; the token
+  // axis is Sq = Sk = L = T of B = 1
+  uint64_t cu = 0;
+  int64_t n = 0;
 };
+
+constexpr int64_t kFlashMaxSeqs = 65536;
 
 [[noreturn]] void refuse(const std::string& what) { throw std::invalid_argument("flash_attention: " + what); }
 
@@ -596,6 +669,14 @@ void check(const Problem& p) {
   // kSelf takes Sk = Sq and q_pos0 = 0 as compile-time facts and reads neither from the arguments
   if (p.self && (p.Sq != p.Sk || p.L != p.Sk || p.q_pos0 != 0))
     refuse("self-attention needs Sq = Sk = seg_len and q_pos0 = 0");
+  if (!p.cu && p.n) refuse("sequences without cu_seqlens");
+  if (p.cu) {
+    // kVarlen takes one token axis of T rows and reads n + 1 boundaries; T / BLK + n slots fit any grid
+    if (p.cu % 4) refuse("cu_seqlens must be 4-byte aligned");
+    if (p.n < 1 || p.n > kFlashMaxSeqs) refuse("1 <= n <= 65536 sequences required");
+    if (p.self || p.B != 1 || p.Sq != p.Sk || p.L != p.Sk || p.q_pos0 != 0)
+      refuse("the packed form needs B = 1, Sq = Sk = seg_len = T, q_pos0 = 0 and no self_attention flag");
+  }
 }
 
 // Checks a view and unpacks it into the kernel arguments.
@@ -620,6 +701,10 @@ void fill(Args& a, const Problem& p, const View& q, const View& k, const View& v
   a.Sq = (int)p.Sq;
   a.Sk = (int)p.Sk;
   a.L = (int)p.L;
+  if (p.cu) {  // the two slots kVarlen reads instead (Sq is T)
+    a.n = (int)p.n;
+    a.cu = reinterpret_cast<const int*>(p.cu);
+  }
   a.q_pos0 = (int)p.q_pos0;
   a.Hq = p.Hq;
   a.Hkv = p.Hkv;
@@ -627,11 +712,13 @@ void fill(Args& a, const Problem& p, const View& q, const View& k, const View& v
 }
 
 // Calls f(D, causal, MODE) with the kernels' compile-time values as integral constants.  The mode
-// is the caller's: kSelf on its flag, else kChunk, or kSegmented when the key axis is segmented.
+// is the caller's: kSelf on its flag, kVarlen with boundaries, else kChunk, or kSegmented when the
+// key axis is segmented.
 template <typename F>
 void dispatch(const Problem& p, F&& f) {
   auto by_mode = [&](auto d, auto c) {
     if (p.self) f(d, c, std::integral_constant<int, kSelf>{});
+    else if (p.cu) f(d, c, std::integral_constant<int, kVarlen>{});
     else if (p.L == p.Sk) f(d, c, std::integral_constant<int, kChunk>{});
     else f(d, c, std::integral_constant<int, kSegmented>{});
   };
@@ -641,12 +728,17 @@ void dispatch(const Problem& p, F&& f) {
   if (p.D == 64) by_causal(std::integral_constant<int, 64>{}); else by_causal(std::integral_constant<int, 128>{});
 }
 
-dim3 query_grid(const Problem& p) { return dim3((unsigned)((p.Sq + kFlashBQ - 1) / kFlashBQ), (unsigned)p.Hq, (unsigned)p.B); }
+// Workgroups along a `rows`-long axis cut into blocks of `blk`; the packed form has T / blk + n slots
+// whatever the boundaries hold.
+unsigned blocks(const Problem& p, int64_t rows, int blk) {
+  return (unsigned)(p.cu ? rows / blk + p.n : (rows + blk - 1) / blk);
+}
+dim3 query_grid(const Problem& p) { return dim3(blocks(p, p.Sq, kFlashBQ), (unsigned)p.Hq, (unsigned)p.B); }
 
 void flash_attn_fwd(const View& q, const View& k, const View& v, uint64_t out, uint64_t lse, int B, int64_t Sq, int64_t Sk,
                     int64_t seg_len, int64_t q_pos0, int Hq, int Hkv, int D, bool causal, double scale, bool self_attention,
-                    uint64_t stream) {
-  const Problem p{B, Sq, Sk, seg_len, q_pos0, Hq, Hkv, D, causal, scale, self_attention};
+                    uint64_t stream, uint64_t cu_seqlens, int64_t n_seq) {
+  const Problem p{B, Sq, Sk, seg_len, q_pos0, Hq, Hkv, D, causal, scale, self_attention, cu_seqlens, n_seq};
   FwdArgs a;
   fill(a, p, q, k, v);
   if (out == 0 || out % 16 || lse == 0 || lse % 4) refuse("misaligned out / lse");
@@ -663,22 +755,22 @@ void flash_attn_fwd(const View& q, const View& k, const View& v, uint64_t out, u
 void flash_attn_bwd(const View& dout, const View& q, const View& k, const View& v, uint64_t out, uint64_t lse,
                     uint64_t delta, uint64_t dq, const View& dk, const View& dv, int B, int64_t Sq, int64_t Sk,
                     int64_t seg_len, int64_t q_pos0, int Hq, int Hkv, int D, bool causal, double scale, bool self_attention,
-                    uint64_t stream) {
-  const Problem p{B, Sq, Sk, seg_len, q_pos0, Hq, Hkv, D, causal, scale, self_attention};
+                    uint64_t stream, uint64_t cu_seqlens, int64_t n_seq) {
+  const Problem p{B, Sq, Sk, seg_len, q_pos0, Hq, Hkv, D, causal, scale, self_attention, cu_seqlens, n_seq};
   BwdArgs a;
   fill(a, p, q, k, v);
   if (Hkv > 65535) refuse("Hkv <= 65535 required");  // a grid dimension of the dK/dV kernel
   take("dout", dout, a.dout, a.sdo);
   take("dk", dk, a.dk, a.sdk, &a.dkseg);
   take("dv", dv, a.dv, a.sdv, &a.dvseg);
-  if (self_attention) {
-    // the kSelf dK/dV store ignores the strides: they must be those of a contiguous [B, S, Hkv, D]
-    // tensor (0 stands for the stride of an axis of length 1)
+  if (self_attention || cu_seqlens) {
+    // the kSelf and kVarlen dK/dV stores ignore the strides: they must be those of a contiguous
+    // [B, S, Hkv, D] tensor (0 stands for the stride of an axis of length 1)
     const Strides want{Sk * Hkv * D, (int64_t)Hkv * D, (int64_t)D};
     auto same = [](int64_t got, int64_t w, int64_t len) { return got == w || (len == 1 && got == 0); };
     for (const Strides* s : {&a.sdk, &a.sdv})
       if (!same(s->b, want.b, B) || !same(s->s, want.s, Sk) || !same(s->h, want.h, Hkv))
-        refuse("self-attention needs contiguous dk / dv");
+        refuse("self-attention and the packed form need contiguous dk / dv");
   }
   if (out == 0 || (out | dq) % 16 || dq == 0 || lse == 0 || delta == 0 || (lse | delta) % 4)
     refuse("misaligned out / lse / delta / dq");
@@ -692,7 +784,7 @@ void flash_attn_bwd(const View& dout, const View& q, const View& k, const View& 
   a.dq = reinterpret_cast<uint16_t*>(dq);
   a.scale = (float)scale;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const dim3 block(kFlashThreads), key_grid((unsigned)((Sk + kFlashBK - 1) / kFlashBK), (unsigned)Hkv, (unsigned)B);
+  const dim3 block(kFlashThreads), key_grid(blocks(p, Sk, kFlashBK), (unsigned)Hkv, (unsigned)B);
   dispatch(p, [&](auto d, auto c, auto m) {
     constexpr int DD = decltype(d)::value, M = decltype(m)::value;
     constexpr bool C = decltype(c)::value;
@@ -713,19 +805,23 @@ void register_flash_attn_ops(pybind11::module_& m) {
         "forward: q [B, Sq, Hq, D] at positions q_pos0.., k / v with Sk keys in segments of seg_len; each a bf16 view "
         "(address, segment stride, b, s, h strides in elements; unit stride on D).  causal: key j visible to row i iff "
         "j <= q_pos0 + i -> out [B, Sq, Hq, D] bf16 contiguous, lse [B, Hq, Sq] fp32.  self_attention: the "
-        "self-attention kernels (Sq = Sk = seg_len, q_pos0 = 0)",
+        "self-attention kernels (Sq = Sk = seg_len, q_pos0 = 0).  cu_seqlens (device address of n_seq + 1 int32 "
+        "boundaries): the packed form, B = 1 and Sq = Sk = seg_len = T tokens, self-attention inside each sequence; "
+        "out [T, Hq, D], lse [Hq, T]",
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("out"), py::arg("lse"), py::arg("B"), py::arg("Sq"),
         py::arg("Sk"), py::arg("seg_len"), py::arg("q_pos0"), py::arg("Hq"), py::arg("Hkv"), py::arg("D"),
-        py::arg("causal"), py::arg("scale"), py::arg("self_attention"), py::arg("stream"),
-        py::call_guard<py::gil_scoped_release>());
+        py::arg("causal"), py::arg("scale"), py::arg("self_attention"), py::arg("stream"), py::arg("cu_seqlens") = 0,
+        py::arg("n_seq") = 0, py::call_guard<py::gil_scoped_release>());
   m.def("flash_attn_bwd", &flash_attn_bwd,
         "backward: delta [B, Hq, Sq] fp32 workspace, dq [B, Sq, Hq, D] bf16 contiguous; dk / dv views like k / v, "
         "written through their own strides (a key no query sees gets exact zeros), contiguous [B, S, Hkv, D] with "
-        "self_attention; three launches (delta, dK/dV, dQ), no atomics",
+        "self_attention and in the packed form (cu_seqlens, n_seq as in the forward: delta [Hq, T], dq [T, Hq, D], "
+        "dk / dv [T, Hkv, D]); three launches (delta, dK/dV, dQ), no atomics",
         py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("out"), py::arg("lse"), py::arg("delta"),
         py::arg("dq"), py::arg("dk"), py::arg("dv"), py::arg("B"), py::arg("Sq"), py::arg("Sk"), py::arg("seg_len"),
         py::arg("q_pos0"), py::arg("Hq"), py::arg("Hkv"), py::arg("D"), py::arg("causal"), py::arg("scale"),
-        py::arg("self_attention"), py::arg("stream"), py::call_guard<py::gil_scoped_release>());
+        py::arg("self_attention"), py::arg("stream"), py::arg("cu_seqlens") = 0, py::arg("n_seq") = 0,
+        py::call_guard<py::gil_scoped_release>());
 }
 
 }  // namespace dev

@@ -984,21 +984,25 @@ _FLASH_MAX_GRID = 65535  # B and Hq are grid dimensions
 
 
 _FLASH_MAX_POS = 1 << 30
-# The two public faces of the one implementation below: (name used in messages, self form).  The
+FLASH_MAX_SEQS = 65536  # sequences of one packed call (kFlashMaxSeqs)
+# The three public faces of the one implementation below: (name used in messages, self form).  The
 # self form is the chunk form with one length, q_pos0 = 0, no segments and contiguous dk / dv; it
-# runs the self-attention instantiations of the kernels.
+# runs the self-attention instantiations of the kernels.  The packed form is the self form on
+# [T, H, D] operands with ``cu_seqlens``: it runs the varlen instantiations.
 _FLASH_SELF = ("flash_attention", True)
 _FLASH_CHUNK = ("flash_attention_chunk", False)
+_FLASH_VARLEN = ("flash_attention_varlen", True)
 
 
 def flash_is_view(t) -> bool:
-    """Whether a [B, S, H, D] tensor can be read as it is (the stride rules of ``_flash_view_check``)."""
-    return (t.stride(3) == 1 and all(t.shape[ax] == 1 or t.stride(ax) % 8 == 0 for ax in range(3))
+    """Whether a [B, S, H, D] (packed: [T, H, D]) tensor can be read as it is (the stride rules of
+    ``_flash_view_check``)."""
+    return (t.stride(-1) == 1 and all(t.shape[ax] == 1 or t.stride(ax) % 8 == 0 for ax in range(t.dim() - 1))
             and t.data_ptr() % 16 == 0)
 
 
 def _flash_view_check(public: str, name: str, t) -> None:
-    """The stride rules of an operand read as a view, [B, S, H, D] or segmented [n, B, L, H, D]:
+    """The stride rules of an operand read as a view, [B, S, H, D], packed [T, H, D] or segmented [n, B, L, H, D]:
     unit stride on D, every other stride (of an axis longer than 1) a multiple of 8 elements,
     16-byte-aligned base."""
     shape, stride = t.shape, t.stride()
@@ -1014,17 +1018,35 @@ def _flash_view_check(public: str, name: str, t) -> None:
 
 def _flash_view(t):
     """A view as the extension takes it: (address, segment, batch, row, head stride) in elements;
-    0 for an axis of length 1 and for the segment stride of a 4-D tensor."""
+    0 for an axis of length 1 and for the axes a 4-D (no segments) or packed 3-D (one batch entry)
+    tensor does not have."""
     st = [s if n > 1 else 0 for n, s in zip(t.shape[:-1], t.stride())]
-    return (t.data_ptr(), *st) if len(st) == 4 else (t.data_ptr(), 0, *st)
+    return (t.data_ptr(), *[0] * (4 - len(st)), *st)
 
 
-def _flash_validate(public: str, self_form: bool, q, k, v, q_pos0=0, kv_segment=None):
-    """The one rule list behind ``flash_attention_validate`` and ``flash_attention_chunk_validate``;
-    returns ``(B, Sq, Sk, L, Hq, Hkv, D)``.  The self form adds one rule: k and v have the length of q."""
+def _flash_validate(public: str, self_form: bool, q, k, v, q_pos0=0, kv_segment=None, cu_seqlens=None):
+    """The one rule list behind ``flash_attention_validate``, ``flash_attention_chunk_validate`` and
+    ``flash_attention_varlen_validate``; returns ``(B, Sq, Sk, L, Hq, Hkv, D)``.  The self form adds
+    one rule: k and v have the length of q.  With ``cu_seqlens`` the operands are packed [T, H, D]:
+    they go through the rules as the one batch entry [1, T, H, D] they are (B = 1, Sq = Sk = T)."""
     for name, t in (("q", q), ("k", k), ("v", v)):
         if t.dtype != torch.bfloat16:
             raise TypeError(f"{public} expects bf16 {name}, got {t.dtype}")
+    if cu_seqlens is not None:
+        if not isinstance(cu_seqlens, torch.Tensor) or cu_seqlens.dtype != torch.int32:
+            raise TypeError(f"{public}: cu_seqlens must be an int32 tensor, got "
+                            f"{getattr(cu_seqlens, 'dtype', type(cu_seqlens).__name__)}")
+        for name, t in (("q", q), ("k", k), ("v", v)):
+            if t.dim() != 3:
+                raise ValueError(f"{public}: {name} must be [T, H, D], got {tuple(t.shape)}")
+        if cu_seqlens.dim() != 1 or cu_seqlens.shape[0] < 2 or not cu_seqlens.is_contiguous():
+            raise ValueError(f"{public}: cu_seqlens must be a contiguous [n + 1] tensor with n >= 1, got shape "
+                             f"{tuple(cu_seqlens.shape)}, strides {cu_seqlens.stride()}")
+        if cu_seqlens.shape[0] - 1 > FLASH_MAX_SEQS:
+            raise ValueError(f"{public}: at most {FLASH_MAX_SEQS} sequences, got {cu_seqlens.shape[0] - 1}")
+        if cu_seqlens.device != q.device:
+            raise ValueError(f"{public}: cu_seqlens must be on the device of q ({q.device}), got {cu_seqlens.device}")
+        q, k, v = q.unsqueeze(0), k.unsqueeze(0), v.unsqueeze(0)
     if isinstance(q_pos0, bool) or not isinstance(q_pos0, int):
         raise ValueError(f"{public}: q_pos0 must be an int, got {q_pos0!r}")
     segmented = kv_segment is not None
@@ -1132,35 +1154,43 @@ def _flash_scale(scale, D: int) -> float:
     return s
 
 
-def _flash_forward(public, self_form, q, k, v, causal, scale, out, lse, q_pos0=0, kv_segment=None):
-    B, Sq, Sk, L, Hq, Hkv, D = _flash_validate(public, self_form, q, k, v, q_pos0, kv_segment)
+def _flash_packing(cu_seqlens):
+    """The extension's last two arguments: (address of the boundaries, sequences), (0, 0) when not packed."""
+    return (0, 0) if cu_seqlens is None else (cu_seqlens.data_ptr(), cu_seqlens.shape[0] - 1)
+
+
+def _flash_forward(public, self_form, q, k, v, causal, scale, out, lse, q_pos0=0, kv_segment=None, cu_seqlens=None):
+    B, Sq, Sk, L, Hq, Hkv, D = _flash_validate(public, self_form, q, k, v, q_pos0, kv_segment, cu_seqlens)
     sc = _flash_scale(scale, D)
-    out = _flash_result("out", out, (B, Sq, Hq, D), torch.bfloat16, q)
-    lse = _flash_result("lse", lse, (B, Hq, Sq), torch.float32, q)
+    lead = (B,) if cu_seqlens is None else ()  # packed: out [T, Hq, D], lse [Hq, T]
+    out = _flash_result("out", out, (*lead, Sq, Hq, D), torch.bfloat16, q)
+    lse = _flash_result("lse", lse, (*lead, Hq, Sq), torch.float32, q)
     _D().flash_attn_fwd(_flash_view(q), _flash_view(k), _flash_view(v), out.data_ptr(), lse.data_ptr(), B, Sq, Sk, L,
-                        q_pos0, Hq, Hkv, D, bool(causal), sc, self_form, _stream(q))
+                        q_pos0, Hq, Hkv, D, bool(causal), sc, self_form and cu_seqlens is None, _stream(q),
+                        *_flash_packing(cu_seqlens))
     return out, lse
 
 
 def _flash_backward(public, self_form, dout, q, k, v, out, lse, causal, scale, dq, dk, dv, delta, q_pos0=0,
-                    kv_segment=None):
-    B, Sq, Sk, L, Hq, Hkv, D = _flash_validate(public, self_form, q, k, v, q_pos0, kv_segment)
+                    kv_segment=None, cu_seqlens=None):
+    B, Sq, Sk, L, Hq, Hkv, D = _flash_validate(public, self_form, q, k, v, q_pos0, kv_segment, cu_seqlens)
     sc = _flash_scale(scale, D)
+    lead = (B,) if cu_seqlens is None else ()  # packed: [T, Hq, D] and [Hq, T]
     if dout.dtype != torch.bfloat16:
         raise TypeError(f"{public} expects bf16 dout, got {dout.dtype}")
-    if tuple(dout.shape) != (B, Sq, Hq, D) or dout.device != q.device:
-        raise ValueError(f"{public}: dout must be {(B, Sq, Hq, D)} on {q.device}, got {tuple(dout.shape)}")
+    if tuple(dout.shape) != (*lead, Sq, Hq, D) or dout.device != q.device:
+        raise ValueError(f"{public}: dout must be {(*lead, Sq, Hq, D)} on {q.device}, got {tuple(dout.shape)}")
     _flash_view_check(public, "dout", dout)
     if out is None or lse is None:
         raise ValueError(f"{public}_backward needs the forward's out and lse")
-    out = _flash_result("out", out, (B, Sq, Hq, D), torch.bfloat16, q)
-    lse = _flash_result("lse", lse, (B, Hq, Sq), torch.float32, q)
+    out = _flash_result("out", out, (*lead, Sq, Hq, D), torch.bfloat16, q)
+    lse = _flash_result("lse", lse, (*lead, Hq, Sq), torch.float32, q)
 
     def result(name, t):
         if name == "dq":
-            return _flash_result(name, t, (B, Sq, Hq, D), torch.bfloat16, q)
+            return _flash_result(name, t, (*lead, Sq, Hq, D), torch.bfloat16, q)
         if name == "delta":
-            return _flash_result(name, t, (B, Hq, Sq), torch.float32, q)
+            return _flash_result(name, t, (*lead, Hq, Sq), torch.float32, q)
         # dk / dv: contiguous in the self form (its kernels ignore their strides), views like k in the chunk form
         return _flash_result(name, t, k.shape, torch.bfloat16, q) if self_form else _flash_kv_result(name, t, k)
 
@@ -1173,15 +1203,17 @@ def _flash_backward(public, self_form, dout, q, k, v, out, lse, causal, scale, d
     dq, dk, dv, delta = (result(name, t) for name, t in given.items())
     _D().flash_attn_bwd(_flash_view(dout), _flash_view(q), _flash_view(k), _flash_view(v), out.data_ptr(),
                         lse.data_ptr(), delta.data_ptr(), dq.data_ptr(), _flash_view(dk), _flash_view(dv), B, Sq, Sk, L,
-                        q_pos0, Hq, Hkv, D, bool(causal), sc, self_form, _stream(q))
+                        q_pos0, Hq, Hkv, D, bool(causal), sc, self_form and cu_seqlens is None, _stream(q),
+                        *_flash_packing(cu_seqlens))
     return dq, dk, dv
 
 
 class _FlashAttention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, causal, scale, form, q_pos0, kv_segment):
-        out, lse = _flash_forward(*form, q, k, v, causal, scale, None, None, q_pos0, kv_segment)
+    def forward(ctx, q, k, v, causal, scale, form, q_pos0, kv_segment, cu_seqlens=None):
+        out, lse = _flash_forward(*form, q, k, v, causal, scale, None, None, q_pos0, kv_segment, cu_seqlens)
         ctx.save_for_backward(q, k, v, out, lse)
+        ctx.cu_seqlens = cu_seqlens  # an index tensor, no gradient: the backward reads it as it is then
         ctx.args = (form, causal, scale, q_pos0, kv_segment)
         ctx.mark_non_differentiable(lse)
         return out, lse
@@ -1194,8 +1226,8 @@ class _FlashAttention(torch.autograd.Function):
         if not flash_is_view(dout):  # e.g. an expanded or transposed gradient
             dout = dout.contiguous()
         dq, dk, dv = _flash_backward(*form, dout, q, k, v, out, lse, causal, scale, None, None, None, None, q_pos0,
-                                     kv_segment)
-        return dq, dk, dv, None, None, None, None, None
+                                     kv_segment, ctx.cu_seqlens)
+        return dq, dk, dv, None, None, None, None, None, None
 
 
 def flash_attention_forward(q, k, v, causal: bool = True, scale: Optional[float] = None, out=None, lse=None):
@@ -1261,3 +1293,95 @@ def flash_attention_chunk(q, k, v, causal: bool = True, scale: Optional[float] =
     segmented) and are this chunk's share."""
     flash_attention_chunk_validate(q, k, v, q_pos0, kv_segment)
     return _FlashAttention.apply(q, k, v, bool(causal), scale, _FLASH_CHUNK, q_pos0, kv_segment)[0]
+
+
+# The packed form: sequences of different lengths back to back on one token axis.
+def flash_attention_varlen_validate(q, k, v, cu_seqlens):
+    """Argument rules of ``flash_attention_varlen`` that need no GPU; raises TypeError (dtypes,
+    ``cu_seqlens`` included) / ValueError (everything else) and returns ``(T, n, Hq, Hkv, D)``.
+
+    ``q`` is [T, Hq, D], ``k`` and ``v`` [T, Hkv, D], all bf16 views under the rules of
+    ``flash_attention_validate`` (column slices of a fused [T, (Hq + 2 Hkv) D] buffer qualify),
+    ``1 <= T <= 2^30``.  ``cu_seqlens`` is a contiguous int32 [n + 1] tensor on the device of ``q``,
+    ``1 <= n <= 65536``: sequence ``i`` owns rows ``[cu[i], cu[i + 1])`` of all three operands.  Its
+    CONTENTS are the caller's promise (``cu[0] = 0``, nondecreasing, ``cu[n] <= T``; zero lengths
+    are legal) and are read on the device only: the kernels clamp them, so nothing outside the
+    tensors is touched whatever they hold, ``cu[n] > T`` truncates the last sequence at ``T``,
+    and any other broken promise gives unspecified values."""
+    _, T, _, _, Hq, Hkv, D = _flash_validate(*_FLASH_VARLEN, q, k, v, cu_seqlens=_flash_boundaries(cu_seqlens))
+    return T, int(cu_seqlens.shape[0]) - 1, Hq, Hkv, D
+
+
+def _flash_boundaries(cu_seqlens):
+    """``cu_seqlens`` of a packed call: never None, which would select the self form."""
+    if cu_seqlens is None:
+        raise TypeError("flash_attention_varlen: cu_seqlens must be an int32 tensor, got None")
+    return cu_seqlens
+
+
+def flash_varlen_tile_map(cu_seqlens, block: int, T: Optional[int] = None):
+    """Host mirror of the packed kernels' slot map: one entry per slot of the grid's x axis,
+    ``(sequence, tile, begin, end)`` for the workgroup that computes rows (``block = FLASH_BQ``:
+    forward, dQ) or keys (``block = FLASH_BK``: dK/dV) ``[tile * block, (tile + 1) * block)`` of the
+    sequence on rows ``[begin, end)`` of the token axis, ``None`` for a spare slot, which leaves at
+    once.  ``cu_seqlens`` is a CPU tensor or a list of n + 1 boundaries, ``T`` the length of the
+    token axis (default ``cu_seqlens[-1]``).  As in the kernel: ``begin = clamp(cu[i], 0, T)``,
+    ``end = clamp(cu[i + 1], begin, T)``, sequence ``i`` owns the slots from ``begin // block + i``
+    on, there are ``T // block + n`` slots, and a slot's sequence is found by bisection."""
+    cu = [int(x) for x in (cu_seqlens.tolist() if isinstance(cu_seqlens, torch.Tensor) else cu_seqlens)]
+    block, n = int(block), len(cu) - 1
+    if block < 1 or n < 1:
+        raise ValueError("flash_varlen_tile_map: block must be positive and cu_seqlens hold at least 2 boundaries")
+    T = cu[-1] if T is None else int(T)
+    if T < 1:
+        raise ValueError(f"flash_varlen_tile_map: T must be positive, got {T}")
+
+    def at(i):
+        return min(max(cu[i], 0), T)
+
+    slots = []
+    for slot in range(T // block + n):
+        lo, hi = 0, n
+        while hi - lo > 1:
+            mid = (lo + hi) >> 1
+            if at(mid) // block + mid <= slot:
+                lo = mid
+            else:
+                hi = mid
+        begin = at(lo)
+        end = max(at(lo + 1), begin)
+        tile = slot - (begin // block + lo)
+        slots.append(None if tile < 0 or tile * block >= end - begin else (lo, tile, begin, end))
+    return slots
+
+
+def flash_attention_varlen_forward(q, k, v, cu_seqlens, causal: bool = True, scale: Optional[float] = None, out=None,
+                                   lse=None):
+    """``flash_attention_forward`` inside every sequence of a packed token axis: ``q`` [T, Hq, D],
+    ``k`` / ``v`` [T, Hkv, D] and ``cu_seqlens`` as ``flash_attention_varlen_validate`` describes.
+    A row sees the keys of its own sequence only (those up to itself with ``causal``).  Returns
+    ``(out [T, Hq, D] bf16 contiguous, lse [Hq, T] fp32)``; the rows of a sequence are bitwise what
+    ``flash_attention_forward`` returns for that sequence alone, and rows from ``cu[n]`` on are not
+    written.  The boundaries are read on the device: no host synchronisation, no allocation when
+    ``out`` and ``lse`` are passed, and a captured graph follows the contents of ``cu_seqlens``."""
+    return _flash_forward(*_FLASH_VARLEN, q, k, v, causal, scale, out, lse, cu_seqlens=_flash_boundaries(cu_seqlens))
+
+
+def flash_attention_varlen_backward(dout, q, k, v, cu_seqlens, out, lse, causal: bool = True,
+                                    scale: Optional[float] = None, dq=None, dk=None, dv=None, delta=None):
+    """``(dq, dk, dv)`` of ``flash_attention_varlen_forward``: ``dq`` [T, Hq, D], ``dk`` / ``dv``
+    [T, Hkv, D] bf16 contiguous, ``delta`` [Hq, T] fp32 the workspace; ``dout`` follows the stride
+    rules of ``q``.  The rows of a sequence are bitwise ``flash_attention_backward`` of that
+    sequence alone; rows from ``cu[n]`` on are not written.  With ``dq``, ``dk``, ``dv`` and
+    ``delta`` passed the call allocates nothing and never synchronises with the host."""
+    return _flash_backward(*_FLASH_VARLEN, dout, q, k, v, out, lse, causal, scale, dq, dk, dv, delta,
+                           cu_seqlens=_flash_boundaries(cu_seqlens))
+
+
+def flash_attention_varlen(q, k, v, cu_seqlens, causal: bool = True, scale: Optional[float] = None):
+    """Differentiable ``flash_attention_varlen_forward``: ``out`` [T, Hq, D] bf16, differentiable in
+    ``q``, ``k`` and ``v``.  Rows from ``cu_seqlens[n]`` on belong to no sequence: they are left
+    unwritten and their gradients too, so the caller keeps them out of the loss and of the
+    parameters' gradients (pack to ``cu_seqlens[n] = T``)."""
+    flash_attention_varlen_validate(q, k, v, cu_seqlens)
+    return _FlashAttention.apply(q, k, v, bool(causal), scale, _FLASH_VARLEN, 0, None, cu_seqlens)[0]

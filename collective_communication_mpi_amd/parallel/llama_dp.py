@@ -23,6 +23,11 @@ model on its shard of consecutive positions and the block calls ``context_parall
 (parallel/context_parallel.py); everything else in the block is per token.  The caller passes
 explicit ``targets`` (a shard's last target lives on the next rank) and averages the parameter
 gradients over ``cp``.
+With ``cu_seqlens`` (int32 [n + 1] on the device, "flash" without ``cp``) the batch is PACKED:
+the boundaries are positions on the flattened ``batch * seq`` token axis, document ``i`` owns
+tokens ``[cu_seqlens[i], cu_seqlens[i + 1])`` with ``cu_seqlens[n] = batch * seq``, and the block
+calls ``ops.flash_attention_varlen``, so no token sees another document.  The caller passes explicit
+``targets`` with -100 (``F.cross_entropy``'s ``ignore_index``) at each document's last token.
 RoPE is left out (no effect on gradient sizes or the GEMM work).  Random-init weights,
 synthetic token ids.
 """
@@ -35,7 +40,7 @@ from typing import Dict, List, Optional
 import torch
 import torch.nn.functional as F
 
-from ..ops.kernels import FLASH_HEAD_DIMS, flash_attention
+from ..ops.kernels import FLASH_HEAD_DIMS, flash_attention, flash_attention_varlen
 from .context_parallel import context_parallel_attention
 from .ddp import DistributedDataParallel
 from .tensor_parallel import ColumnParallelLinear, ParallelSwiGLUMLP, RowParallelLinear
@@ -97,9 +102,19 @@ class LlamaBlock(torch.nn.Module):
         self.mlp_norm = RMSNorm(d, cfg.eps, device, dtype)
         self.mlp = ParallelSwiGLUMLP(d, cfg.ffn, tp, device=device, dtype=dtype, seed=seed + 4, init="device")
 
-    def forward(self, x, batch: int, seq: int):
+    def forward(self, x, batch: int, seq: int, cu_seqlens: Optional[torch.Tensor] = None):
         cfg = self.cfg
         hd = cfg.head_dim
+        if cu_seqlens is not None:  # packed documents: boundaries on the flattened batch * seq token axis
+            if cfg.attention != "flash" or self.cp is not None:
+                raise ValueError('cu_seqlens needs attention="flash" and no context parallelism (cp), got '
+                                 f"attention={cfg.attention!r}, cp {'set' if self.cp is not None else 'None'}")
+            n = self.attn_norm(x)
+            o = flash_attention_varlen(self.wq(n).view(batch * seq, cfg.heads, hd),
+                                       self.wk(n).view(batch * seq, cfg.kv_heads, hd),
+                                       self.wv(n).view(batch * seq, cfg.kv_heads, hd), cu_seqlens, causal=True)
+            h = x + self.wo(o.view(batch * seq, cfg.d))
+            return h + self.mlp(self.mlp_norm(h))
         n = self.attn_norm(x)
         if cfg.attention == "flash":  # the projections' views as they are; K and V stay at kv_heads
             q, k, v = (self.wq(n).view(batch, seq, cfg.heads, hd), self.wk(n).view(batch, seq, cfg.kv_heads, hd),
@@ -125,7 +140,9 @@ class LlamaBlock(torch.nn.Module):
 
 class LlamaModel(torch.nn.Module):
     """Token ids [batch, seq] -> mean next-token cross-entropy (fp32).  With ``cp``, ``ids`` (and
-    ``targets``) are this rank's shard of consecutive positions and the loss is the shard's mean."""
+    ``targets``) are this rank's shard of consecutive positions and the loss is the shard's mean.
+    With ``cu_seqlens`` the ``batch * seq`` tokens are packed documents (module docstring): pass
+    ``targets`` with -100 at each document's last token."""
 
     def __init__(self, cfg: LlamaConfig, tp, device, dtype=torch.bfloat16, seed: int = 0, vocab: bool = True,
                  cp=None):
@@ -144,11 +161,12 @@ class LlamaModel(torch.nn.Module):
             self.head = ColumnParallelLinear(cfg.d, cfg.vocab, tp, bias=False, device=device, dtype=dtype,
                                              seed=seed + 7, init="device")
 
-    def forward(self, ids, x0: Optional[torch.Tensor] = None, targets: Optional[torch.Tensor] = None):
+    def forward(self, ids, x0: Optional[torch.Tensor] = None, targets: Optional[torch.Tensor] = None,
+                cu_seqlens: Optional[torch.Tensor] = None):
         b, s = ids.shape
         x = self.embed(ids).view(b * s, self.cfg.d) if self.vocab else x0
         for blk in self.blocks:
-            x = blk(x, b, s)
+            x = blk(x, b, s, cu_seqlens)
         x = self.norm(x)
         if not self.vocab:
             return x.float().pow(2).mean()
