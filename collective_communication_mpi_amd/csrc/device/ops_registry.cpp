@@ -14,6 +14,7 @@ void register_grouped_gemm_ops(pybind11::module_& m);
 void register_moe_gate_ops(pybind11::module_& m);
 void register_moe_router_ops(pybind11::module_& m);
 void register_flash_attn_ops(pybind11::module_& m);
+void register_xent_ops(pybind11::module_& m);
 
 void register_ops(pybind11::module_& m) {
   register_layout_ops(m);
@@ -26,6 +27,7 @@ void register_ops(pybind11::module_& m) {
   register_moe_gate_ops(m);
   register_moe_router_ops(m);
   register_flash_attn_ops(m);
+  register_xent_ops(m);
 }
 
 }  // namespace dev

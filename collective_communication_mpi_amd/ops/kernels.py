@@ -1385,3 +1385,264 @@ def flash_attention_varlen(q, k, v, cu_seqlens, causal: bool = True, scale: Opti
     parameters' gradients (pack to ``cu_seqlens[n] = T``)."""
     flash_attention_varlen_validate(q, k, v, cu_seqlens)
     return _FlashAttention.apply(q, k, v, bool(causal), scale, _FLASH_VARLEN, 0, None, cu_seqlens)[0]
+
+
+# ---------------------------------------------------------------------------
+# fused cross-entropy over a shard of the vocabulary (csrc/device/xent.hip)
+# ---------------------------------------------------------------------------
+XENT_SWEEP = 2048  # columns one workgroup covers per sweep (csrc/device/xent.hpp kXentSweep): 256 threads x 8 bf16
+XENT_CHUNK = 256   # rows per workgroup of the combine kernel (kXentChunk): fixes loss_sum's summation order
+XENT_MAX_PARTIALS = 1024  # partials of one row: 16 ranks x 64 splits
+_XENT_TARGET_GROUPS = 1024  # kXentTargetGroups
+_XENT_MIN_SWEEPS = 4        # kXentMinSweeps
+_XENT_MAX_SPLITS = 64       # kXentMaxSplits
+
+
+def _xent_split_sweeps(T: int, Vloc: int) -> int:
+    n = (Vloc + XENT_SWEEP - 1) // XENT_SWEEP
+    want = 1 if T >= _XENT_TARGET_GROUPS else (_XENT_TARGET_GROUPS + T - 1) // T
+    want = max(1, min(want, n // _XENT_MIN_SWEEPS, _XENT_MAX_SPLITS))
+    return (n + want - 1) // want
+
+
+def xent_row_splits(T: int, Vloc: int) -> int:
+    """Column splits of one row in the cross-entropy kernels: split ``i`` covers the columns
+    ``[i w, min((i + 1) w, Vloc))`` with ``w`` a whole number of ``XENT_SWEEP`` sweeps.  A pure
+    function of ``(T, Vloc)`` (the mirror of csrc/device/xent.hpp, which the launcher checks) --
+    never of the device or the grid: every split writes a partial of its own and the merge order
+    is part of the result's bits.  1 whenever ``T >= 1024`` or ``Vloc <= 7 XENT_SWEEP``."""
+    T, Vloc = int(T), int(Vloc)
+    if T < 1 or Vloc < 1:
+        raise ValueError(f"xent_row_splits: T and Vloc must be positive, got {T}, {Vloc}")
+    per = _xent_split_sweeps(T, Vloc)
+    return ((Vloc + XENT_SWEEP - 1) // XENT_SWEEP + per - 1) // per
+
+
+def _xent_logits_rules(name: str, t) -> None:
+    """[T, Vloc] bf16, unit column stride, row stride and Vloc multiples of 8, 16-byte-aligned base."""
+    if t.dtype != torch.bfloat16:
+        raise TypeError(f"cross_entropy expects bf16 {name}, got {t.dtype}")
+    if t.dim() != 2:
+        raise ValueError(f"cross_entropy: {name} must be [T, Vloc], got {tuple(t.shape)}")
+    T, V = t.shape
+    if T < 1:
+        raise ValueError(f"cross_entropy: {name} needs at least one row (T >= 1)")
+    if T >= 1 << 31:
+        raise ValueError("cross_entropy: T must be below 2^31")
+    if V < 8 or V % 8 or V >= (1 << 31) - XENT_SWEEP:
+        raise ValueError(f"cross_entropy: Vloc must be a positive multiple of 8 below 2^31 - {XENT_SWEEP}, got {V}")
+    if t.stride(1) != 1:
+        raise ValueError(f"cross_entropy: {name} must have unit column stride, got {t.stride(1)}")
+    if t.stride(0) % 8 or (T > 1 and t.stride(0) < V):
+        raise ValueError(f"cross_entropy: the row stride of {name} must be a multiple of 8 and at least Vloc, got "
+                         f"{t.stride(0)}")
+    if t.data_ptr() % 16:
+        raise ValueError(f"cross_entropy: {name} must start at a 16-byte-aligned address")
+
+
+def cross_entropy_validate(logits, targets, vocab_start: int = 0):
+    """Argument rules of the cross-entropy ops that need no GPU; raises TypeError (dtypes) /
+    ValueError (the rest) and returns ``(T, Vloc)``: ``logits`` [T, Vloc] bf16 with unit column
+    stride, row stride and ``Vloc`` multiples of 8, a 16-byte-aligned base and ``T >= 1`` (the
+    head GEMM's output as it is, or a column / row view of a larger buffer); ``targets`` [T] int64,
+    contiguous, on the logits' device, in GLOBAL vocabulary numbering; ``vocab_start >= 0`` the
+    global index of column 0."""
+    if targets.dtype != torch.int64:
+        raise TypeError(f"cross_entropy expects int64 targets, got {targets.dtype}")
+    _xent_logits_rules("logits", logits)
+    T, V = logits.shape
+    if targets.dim() != 1 or targets.shape[0] != T or not targets.is_contiguous():
+        raise ValueError(f"cross_entropy: targets must be a contiguous [{T}] tensor, got {tuple(targets.shape)}")
+    if targets.device != logits.device:
+        raise ValueError(f"cross_entropy: targets are on {targets.device}, logits on {logits.device}")
+    if int(vocab_start) < 0 or int(vocab_start) > 1 << 62:
+        raise ValueError(f"cross_entropy: vocab_start must be in [0, 2^62], got {vocab_start}")
+    return int(T), int(V)
+
+
+def _xent_buffer(name: str, t, shape, dtype, device, align: int = 1):
+    """A caller's buffer (exact shape, dtype, contiguous, on ``device``) or a fresh one."""
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if t.dtype != dtype:
+        raise TypeError(f"cross_entropy: {name} must be {dtype}, got {t.dtype}")
+    if tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"cross_entropy: {name} must be a contiguous {tuple(shape)} tensor, got {tuple(t.shape)}")
+    if t.device != device:
+        raise ValueError(f"cross_entropy: {name} is on {t.device}, expected {device}")
+    if t.data_ptr() % align:
+        raise ValueError(f"cross_entropy: {name} must start at a {align}-byte-aligned address")
+    return t
+
+
+def cross_entropy_stats(logits, targets, vocab_start: int = 0, stats=None):
+    """One read pass over ``logits`` (``k_xent_stats``): ``stats`` [splits, T, 4] fp32 with
+    ``splits = xent_row_splits(T, Vloc)``, row ``t`` of split ``i`` holding ``(m, s, zt, hit)``:
+    the max over the split's columns, the sum of ``exp(z - m)``, the target's logit when
+    ``vocab_start <= target < vocab_start + Vloc`` lies in the split (else 0) and 1.0 / 0.0 for
+    that test.  ``-inf`` logits are legal; an all ``-inf`` split gives ``(-inf, 0)``.  With
+    ``stats`` passed the call allocates nothing and never synchronises with the host."""
+    T, V = cross_entropy_validate(logits, targets, vocab_start)
+    splits = xent_row_splits(T, V)
+    stats = _xent_buffer("stats", stats, (splits, T, 4), torch.float32, logits.device, align=16)
+    _D().xent_stats(logits.data_ptr(), targets.data_ptr(), stats.data_ptr(), T, V, logits.stride(0), int(vocab_start),
+                    splits, _stream(logits))
+    return stats
+
+
+def cross_entropy_combine(stats, targets, ignore_index: int = -100, lse=None, row_loss=None, loss_sum=None,
+                          n_valid=None, *, mean=None, work=None):
+    """Merge the rows' partials (``k_xent_combine`` + ``k_xent_sum``): ``stats`` [P, T, 4] fp32
+    (TP ranks x splits, rank-major), merged IN INDEX ORDER: ``M = max m_i``, ``S = sum s_i
+    exp(m_i - M)``, ``lse = M + log S``, ``zt = sum zt_i``.  Returns ``(lse [T], row_loss [T],
+    loss_sum [1])`` fp32 and ``n_valid [1]`` int64: ``row_loss = lse - zt``, exactly 0 where
+    ``target == ignore_index``; ``loss_sum`` adds the rows of each ``XENT_CHUNK`` chunk in a fixed
+    tree and the chunks in a fixed order (no atomics: the bits depend on T alone).  ``mean`` [1]
+    fp32 (optional) receives ``loss_sum / n_valid``, 0 when no row is valid; ``work``
+    [ceil(T / XENT_CHUNK), 2] fp32 is the chunk workspace.  A target that is neither
+    ``ignore_index`` nor in the vocabulary is the caller's broken promise: values unspecified,
+    addresses safe.  With every buffer passed the call allocates nothing and never synchronises."""
+    if stats.dtype != torch.float32:
+        raise TypeError(f"cross_entropy_combine expects fp32 stats, got {stats.dtype}")
+    if targets.dtype != torch.int64:
+        raise TypeError(f"cross_entropy_combine expects int64 targets, got {targets.dtype}")
+    if stats.dim() != 3 or stats.shape[2] != 4 or stats.shape[0] < 1 or stats.shape[1] < 1 or not stats.is_contiguous():
+        raise ValueError("cross_entropy_combine: stats must be a contiguous [P, T, 4] tensor, got "
+                         f"{tuple(stats.shape)}")
+    P, T = int(stats.shape[0]), int(stats.shape[1])
+    if P > XENT_MAX_PARTIALS:
+        raise ValueError(f"cross_entropy_combine: at most {XENT_MAX_PARTIALS} partials per row, got {P}")
+    if stats.data_ptr() % 16:
+        raise ValueError("cross_entropy_combine: stats must start at a 16-byte-aligned address")
+    if tuple(targets.shape) != (T,) or not targets.is_contiguous() or targets.device != stats.device:
+        raise ValueError(f"cross_entropy_combine: targets must be a contiguous [{T}] tensor on {stats.device}")
+    dev = stats.device
+    lse = _xent_buffer("lse", lse, (T,), torch.float32, dev)
+    row_loss = _xent_buffer("row_loss", row_loss, (T,), torch.float32, dev)
+    loss_sum = _xent_buffer("loss_sum", loss_sum, (1,), torch.float32, dev)
+    n_valid = _xent_buffer("n_valid", n_valid, (1,), torch.int64, dev)
+    if mean is not None:
+        mean = _xent_buffer("mean", mean, (1,), torch.float32, dev)
+    work = _xent_buffer("work", work, ((T + XENT_CHUNK - 1) // XENT_CHUNK, 2), torch.float32, dev)
+    _D().xent_combine(stats.data_ptr(), targets.data_ptr(), lse.data_ptr(), row_loss.data_ptr(), loss_sum.data_ptr(),
+                      n_valid.data_ptr(), 0 if mean is None else mean.data_ptr(), work.data_ptr(), P, T,
+                      int(ignore_index), _stream(stats))
+    return lse, row_loss, loss_sum, n_valid
+
+
+def cross_entropy_backward(logits, targets, lse, n_valid, grad=None, vocab_start: int = 0, ignore_index: int = -100,
+                           dlogits=None):
+    """``dlogits[t, j] = (exp(z[t, j] - lse[t]) - [vocab_start + j == target[t]]) * g / n_valid``
+    (``k_xent_backward``: one read pass, one write pass), the product in fp32, rounded once to
+    bf16.  ``grad`` (``g``, one fp32 element; None: 1) and ``n_valid`` [1] int64 are read on the
+    device.  Ignored rows store exact zeros; with ``n_valid == 0`` the mean loss is defined as 0
+    and every ``dlogits`` is 0 (torch gives NaN there).  ``dlogits`` is [T, Vloc] bf16 under the
+    rules of ``logits`` and may BE ``logits``.  With ``grad`` and ``dlogits`` passed the call
+    allocates nothing and never synchronises with the host."""
+    T, V = cross_entropy_validate(logits, targets, vocab_start)
+    dev = logits.device
+    if lse.dtype != torch.float32 or n_valid.dtype != torch.int64 or (grad is not None and grad.dtype != torch.float32):
+        raise TypeError("cross_entropy_backward expects fp32 lse and grad and int64 n_valid")
+    if tuple(lse.shape) != (T,) or not lse.is_contiguous():
+        raise ValueError(f"cross_entropy_backward: lse must be a contiguous [{T}] tensor, got {tuple(lse.shape)}")
+    if n_valid.numel() != 1 or (grad is not None and grad.numel() != 1):
+        raise ValueError("cross_entropy_backward: n_valid and grad hold one element each")
+    for t in (lse, n_valid, grad, dlogits):
+        if t is not None and t.device != dev:
+            raise ValueError("cross_entropy_backward: every tensor must be on the logits' device")
+    if dlogits is None:
+        dlogits = torch.empty((T, V), dtype=torch.bfloat16, device=dev)
+    else:
+        _xent_logits_rules("dlogits", dlogits)
+        if tuple(dlogits.shape) != (T, V):
+            raise ValueError(f"cross_entropy_backward: dlogits must be {(T, V)}, got {tuple(dlogits.shape)}")
+    if grad is None:
+        grad = torch.ones(1, dtype=torch.float32, device=dev)
+    _D().xent_backward(logits.data_ptr(), targets.data_ptr(), lse.data_ptr(), n_valid.data_ptr(), grad.data_ptr(),
+                       dlogits.data_ptr(), T, V, logits.stride(0), dlogits.stride(0), int(vocab_start),
+                       int(ignore_index), _stream(logits))
+    return dlogits
+
+
+class _CrossEntropy(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, targets, ignore_index):
+        stats = cross_entropy_stats(logits, targets)
+        mean = torch.empty(1, dtype=torch.float32, device=logits.device)
+        lse, _, _, n_valid = cross_entropy_combine(stats, targets, ignore_index, mean=mean)
+        ctx.save_for_backward(logits, targets, lse, n_valid)
+        ctx.ignore_index = ignore_index
+        return mean.view(())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dloss):
+        logits, targets, lse, n_valid = ctx.saved_tensors
+        g = dloss.to(torch.float32).reshape(1)  # stays on the device: no host synchronisation
+        return cross_entropy_backward(logits, targets, lse, n_valid, g, 0, ctx.ignore_index), None, None
+
+
+def cross_entropy(logits, targets, ignore_index: int = -100):
+    """Differentiable mean cross-entropy of ``logits`` [T, V] bf16 against ``targets`` [T] int64
+    over the rows whose target is not ``ignore_index`` (fp32 scalar; 0, with zero gradients, when
+    no row is valid -- torch gives NaN there).  Saves ``logits``, ``lse`` [T] and ``n_valid``; the
+    backward is one ``k_xent_backward`` launch.  No fp32 [T, V] tensor exists at any point.  Sum
+    and per-token reductions: build them from ``cross_entropy_combine``'s ``row_loss``."""
+    cross_entropy_validate(logits, targets)
+    return _CrossEntropy.apply(logits, targets, int(ignore_index))
+
+
+def cross_entropy_merge_reference(stats, targets, ignore_index: int = -100):
+    """The merge rule of ``cross_entropy_combine`` in torch fp64, partials in index order:
+    ``(lse, row_loss, loss_sum, n_valid)``."""
+    st = stats.double()
+    M = st[:, :, 0].max(dim=0).values
+    S = torch.zeros_like(M)
+    zt = torch.zeros_like(M)
+    for i in range(st.shape[0]):
+        m, s = st[i, :, 0], st[i, :, 1]
+        live = m != float("-inf")
+        S = S + torch.where(live, s * torch.exp(torch.where(live, m - M, torch.zeros_like(m))), torch.zeros_like(s))
+        zt = zt + st[i, :, 2]
+    lse = M + torch.log(S)
+    valid = targets != ignore_index
+    row_loss = torch.where(valid, lse - zt, torch.zeros_like(lse))
+    return lse, row_loss, row_loss.sum(), valid.sum()
+
+
+def cross_entropy_reference(logits, targets, vocab_start: int = 0, ignore_index: int = -100, *, grad: float = 1.0,
+                            lse=None, n_valid=None):
+    """The cross-entropy ops in torch fp64 (any device): returns ``(stats [splits, T, 4], lse [T],
+    row_loss [T], dlogits [T, Vloc])``, ``dlogits`` before its rounding to bf16.  ``stats`` follows
+    ``xent_row_splits``; ``lse`` and ``row_loss`` are those of this shard alone (the unsplit
+    ``logsumexp``).  ``dlogits`` uses ``grad``, and the whole vocabulary's ``lse`` / ``n_valid``
+    when they are passed (a shard of a vocab-parallel loss) instead of this shard's own."""
+    z = logits.double()
+    T, V = z.shape
+    col = targets - int(vocab_start)
+    hit = (col >= 0) & (col < V)
+    safe = torch.where(hit, col, torch.zeros_like(col))
+    splits = xent_row_splits(T, V)
+    width = _xent_split_sweeps(T, V) * XENT_SWEEP
+    stats = torch.zeros((splits, T, 4), dtype=torch.float64, device=z.device)
+    for i in range(splits):
+        c0, c1 = i * width, min((i + 1) * width, V)
+        m = z[:, c0:c1].max(dim=1).values
+        live = m != float("-inf")
+        base = torch.where(live, m, torch.zeros_like(m))
+        here = hit & (col >= c0) & (col < c1)
+        stats[i, :, 0] = m
+        stats[i, :, 1] = torch.exp(z[:, c0:c1] - base[:, None]).sum(dim=1)
+        stats[i, :, 2] = torch.where(here, z.gather(1, safe[:, None])[:, 0], torch.zeros_like(m))
+        stats[i, :, 3] = here.double()
+    own_lse = torch.logsumexp(z, dim=1)
+    valid = targets != ignore_index
+    zt = torch.where(hit, z.gather(1, safe[:, None])[:, 0], torch.zeros_like(own_lse))
+    row_loss = torch.where(valid, own_lse - zt, torch.zeros_like(own_lse))
+    L = own_lse if lse is None else lse.double()
+    n = int(valid.sum()) if n_valid is None else int(n_valid)
+    onehot = torch.zeros_like(z)
+    onehot.scatter_(1, safe[:, None], hit.double()[:, None])
+    scale = float(grad) / n if n > 0 else 0.0
+    dlogits = torch.where(valid[:, None] & (n > 0), (torch.exp(z - L[:, None]) - onehot) * scale, torch.zeros_like(z))
+    return stats, own_lse, row_loss, dlogits

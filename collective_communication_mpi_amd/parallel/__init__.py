@@ -27,3 +27,8 @@ from .context_parallel import (  # noqa: F401,E402
     context_parallel_attention_backward,
     context_parallel_attention_forward,
 )
+from .vocab_parallel import (  # noqa: F401,E402
+    vocab_parallel_cross_entropy,
+    vocab_parallel_cross_entropy_backward,
+    vocab_parallel_cross_entropy_forward,
+)

@@ -28,6 +28,18 @@ the boundaries are positions on the flattened ``batch * seq`` token axis, docume
 tokens ``[cu_seqlens[i], cu_seqlens[i + 1])`` with ``cu_seqlens[n] = batch * seq``, and the block
 calls ``ops.flash_attention_varlen``, so no token sees another document.  The caller passes explicit
 ``targets`` with -100 (``F.cross_entropy``'s ``ignore_index``) at each document's last token.
+The loss is chosen by ``LlamaConfig.loss``: "torch" (the default) is ``F.cross_entropy`` on an fp32
+copy of the logits; "fused" is the project's own kernel family (``vocab_parallel_cross_entropy``,
+parallel/vocab_parallel.py, csrc/device/xent.hip): one read pass over the bf16 logits forward, one
+read and one write pass backward, no fp32 [T, vocab] tensor, and -- the head being a
+``ColumnParallelLinear`` over ``tp`` -- each rank reduces its own ``vocab / p`` columns and one
+small all-gather combines the rows' statistics, so the logits are never gathered.  It takes
+explicit ``targets``, -100 entries, ``cp`` and ``cu_seqlens`` as "torch" does; when every target is
+-100 its loss is 0 with zero gradients where torch gives NaN.  A TP group of more than one rank with
+a vocabulary NEEDS "fused": ``F.cross_entropy`` on a ``vocab / p``-wide shard with global targets
+never computed a loss (it indexed past the shard), so that combination is refused at construction.
+Under TP the block's attention runs on this rank's ``heads / p`` query and ``kv_heads / p`` key /
+value heads (``p`` must divide both).
 RoPE is left out (no effect on gradient sizes or the GEMM work).  Random-init weights,
 synthetic token ids.
 """
@@ -43,7 +55,8 @@ import torch.nn.functional as F
 from ..ops.kernels import FLASH_HEAD_DIMS, flash_attention, flash_attention_varlen
 from .context_parallel import context_parallel_attention
 from .ddp import DistributedDataParallel
-from .tensor_parallel import ColumnParallelLinear, ParallelSwiGLUMLP, RowParallelLinear
+from .tensor_parallel import ColumnParallelLinear, ParallelSwiGLUMLP, RowParallelLinear, _size_rank
+from .vocab_parallel import vocab_parallel_cross_entropy
 
 
 @dataclass
@@ -56,6 +69,7 @@ class LlamaConfig:
     layers: int = 32
     eps: float = 1e-5
     attention: str = "sdpa"  # "sdpa" (PyTorch) or "flash" (ops.flash_attention, head dim 64 / 128)
+    loss: str = "torch"  # "torch" (F.cross_entropy on fp32 logits) or "fused" (vocab_parallel_cross_entropy)
 
     @property
     def head_dim(self) -> int:
@@ -69,6 +83,7 @@ class LlamaConfig:
 
 LLAMA3_8B = LlamaConfig()
 ATTENTION_KINDS = ("sdpa", "flash")
+LOSS_KINDS = ("torch", "fused")
 
 
 class RMSNorm(torch.nn.Module):
@@ -93,6 +108,10 @@ class LlamaBlock(torch.nn.Module):
             raise ValueError(f'attention="flash" needs a head dim in {FLASH_HEAD_DIMS}, got {cfg.head_dim}')
         if cp is not None and cfg.attention != "flash":
             raise ValueError(f'context parallelism (cp) needs attention="flash", got {cfg.attention!r}')
+        p = _size_rank(tp)[0]
+        if cfg.heads % p or cfg.kv_heads % p:
+            raise ValueError(f"the TP size {p} must divide heads ({cfg.heads}) and kv_heads ({cfg.kv_heads})")
+        self.heads, self.kv_heads = cfg.heads // p, cfg.kv_heads // p  # this rank's heads
         kw = dict(bias=False, device=device, dtype=dtype, init="device")
         self.attn_norm = RMSNorm(d, cfg.eps, device, dtype)
         self.wq = ColumnParallelLinear(d, d, tp, seed=seed, **kw)
@@ -104,36 +123,35 @@ class LlamaBlock(torch.nn.Module):
 
     def forward(self, x, batch: int, seq: int, cu_seqlens: Optional[torch.Tensor] = None):
         cfg = self.cfg
-        hd = cfg.head_dim
+        hd, hq, hkv = cfg.head_dim, self.heads, self.kv_heads
         if cu_seqlens is not None:  # packed documents: boundaries on the flattened batch * seq token axis
             if cfg.attention != "flash" or self.cp is not None:
                 raise ValueError('cu_seqlens needs attention="flash" and no context parallelism (cp), got '
                                  f"attention={cfg.attention!r}, cp {'set' if self.cp is not None else 'None'}")
             n = self.attn_norm(x)
-            o = flash_attention_varlen(self.wq(n).view(batch * seq, cfg.heads, hd),
-                                       self.wk(n).view(batch * seq, cfg.kv_heads, hd),
-                                       self.wv(n).view(batch * seq, cfg.kv_heads, hd), cu_seqlens, causal=True)
-            h = x + self.wo(o.view(batch * seq, cfg.d))
+            o = flash_attention_varlen(self.wq(n).view(batch * seq, hq, hd), self.wk(n).view(batch * seq, hkv, hd),
+                                       self.wv(n).view(batch * seq, hkv, hd), cu_seqlens, causal=True)
+            h = x + self.wo(o.view(batch * seq, hq * hd))
             return h + self.mlp(self.mlp_norm(h))
         n = self.attn_norm(x)
         if cfg.attention == "flash":  # the projections' views as they are; K and V stay at kv_heads
-            q, k, v = (self.wq(n).view(batch, seq, cfg.heads, hd), self.wk(n).view(batch, seq, cfg.kv_heads, hd),
-                       self.wv(n).view(batch, seq, cfg.kv_heads, hd))
+            q, k, v = (self.wq(n).view(batch, seq, hq, hd), self.wk(n).view(batch, seq, hkv, hd),
+                       self.wv(n).view(batch, seq, hkv, hd))
             if self.cp is not None:  # seq is this rank's shard; K | V of the other shards are gathered
                 o = context_parallel_attention(self.cp, q, k, v, causal=True)
             else:
                 o = flash_attention(q, k, v, causal=True)
-            h = x + self.wo(o.view(batch * seq, cfg.d))
+            h = x + self.wo(o.view(batch * seq, hq * hd))
             return h + self.mlp(self.mlp_norm(h))
-        q = self.wq(n).view(batch, seq, cfg.heads, hd).transpose(1, 2)
-        k = self.wk(n).view(batch, seq, cfg.kv_heads, hd).transpose(1, 2)
-        v = self.wv(n).view(batch, seq, cfg.kv_heads, hd).transpose(1, 2)
-        rep = cfg.heads // cfg.kv_heads
+        q = self.wq(n).view(batch, seq, hq, hd).transpose(1, 2)
+        k = self.wk(n).view(batch, seq, hkv, hd).transpose(1, 2)
+        v = self.wv(n).view(batch, seq, hkv, hd).transpose(1, 2)
+        rep = hq // hkv
         if rep > 1:  # GQA: expand the kv heads (keeps SDPA on its fused path)
             k = k.repeat_interleave(rep, dim=1)
             v = v.repeat_interleave(rep, dim=1)
         o = F.scaled_dot_product_attention(q, k, v, is_causal=True)
-        o = o.transpose(1, 2).reshape(batch * seq, cfg.d)
+        o = o.transpose(1, 2).reshape(batch * seq, hq * hd)
         h = x + self.wo(o)
         return h + self.mlp(self.mlp_norm(h))
 
@@ -142,13 +160,21 @@ class LlamaModel(torch.nn.Module):
     """Token ids [batch, seq] -> mean next-token cross-entropy (fp32).  With ``cp``, ``ids`` (and
     ``targets``) are this rank's shard of consecutive positions and the loss is the shard's mean.
     With ``cu_seqlens`` the ``batch * seq`` tokens are packed documents (module docstring): pass
-    ``targets`` with -100 at each document's last token."""
+    ``targets`` with -100 at each document's last token.  ``cfg.loss`` picks the loss (module
+    docstring): "fused" is a collective over ``tp`` and the only choice when ``tp`` has more than
+    one rank."""
 
     def __init__(self, cfg: LlamaConfig, tp, device, dtype=torch.bfloat16, seed: int = 0, vocab: bool = True,
                  cp=None):
         super().__init__()
         self.cfg = cfg
         self.vocab = vocab
+        self.tp = tp
+        if cfg.loss not in LOSS_KINDS:
+            raise ValueError(f"LlamaConfig.loss must be one of {LOSS_KINDS}, got {cfg.loss!r}")
+        if vocab and cfg.loss == "torch" and _size_rank(tp)[0] > 1:
+            raise ValueError(f'a TP group of {_size_rank(tp)[0]} ranks shards the vocabulary: it needs loss="fused" '
+                             '(loss="torch" would index past the shard)')
         if vocab:
             self.embed = torch.nn.Embedding(cfg.vocab, cfg.d, device=device, dtype=dtype)
             with torch.no_grad():
@@ -174,6 +200,8 @@ class LlamaModel(torch.nn.Module):
         # explicit targets [batch, seq] replace the roll (context parallel: a shard's last target is
         # the next rank's first id)
         tgt = (torch.roll(ids, -1, dims=1) if targets is None else targets).reshape(-1)
+        if self.cfg.loss == "fused":
+            return vocab_parallel_cross_entropy(self.tp, logits, tgt.contiguous())
         return F.cross_entropy(logits.float(), tgt)
 
 
