@@ -15,6 +15,7 @@ void register_moe_gate_ops(pybind11::module_& m);
 void register_moe_router_ops(pybind11::module_& m);
 void register_flash_attn_ops(pybind11::module_& m);
 void register_xent_ops(pybind11::module_& m);
+void register_rope_ops(pybind11::module_& m);
 
 void register_ops(pybind11::module_& m) {
   register_layout_ops(m);
@@ -28,6 +29,7 @@ void register_ops(pybind11::module_& m) {
   register_moe_router_ops(m);
   register_flash_attn_ops(m);
   register_xent_ops(m);
+  register_rope_ops(m);
 }
 
 }  // namespace dev

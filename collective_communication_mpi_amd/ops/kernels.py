@@ -1646,3 +1646,231 @@ def cross_entropy_reference(logits, targets, vocab_start: int = 0, ignore_index:
     scale = float(grad) / n if n > 0 else 0.0
     dlogits = torch.where(valid[:, None] & (n > 0), (torch.exp(z - L[:, None]) - onehot) * scale, torch.zeros_like(z))
     return stats, own_lse, row_loss, dlogits
+
+
+# ---------------------------------------------------------------------------
+# rotary position embedding (csrc/device/rope.hip)
+# ---------------------------------------------------------------------------
+ROPE_MAX_SEQS = 65536  # sequences of one packed call (csrc/device/rope.hpp kRopeMaxSeqs)
+ROPE_MAX_TOKENS = 1 << 30
+ROPE_MAX_HEADS = 65535  # of q and of k, each (the extension's limit)
+ROPE_MAX_LANES = 64  # head lanes of a token (csrc/device/rope.hpp kRopeMaxLanes)
+ROPE_MAX_THREADS = 256 * (2 ** 31 - 1)  # tokens x D / 16 x head lanes: workgroups of 256 threads on a 31-bit grid
+
+
+def rope_table(n_pos: int, D: int, theta: float = 500000.0, inv_freq=None, device=None):
+    """The ``[n_pos, 2, D / 2]`` fp32 table ``ops.rope_apply`` reads: ``table[p, 0, j] = cos(p f_j)``,
+    ``table[p, 1, j] = sin(p f_j)`` with ``f_j = theta^(-2 j / D)``, computed in fp64 on the CPU and
+    rounded once to fp32.  ``inv_freq`` ([D / 2] float64) replaces the formula: any frequency
+    scaling is a matter of the table, the kernel never sees an angle."""
+    if isinstance(n_pos, bool) or not isinstance(n_pos, int) or n_pos < 1:
+        raise ValueError(f"rope_table: n_pos must be a positive int, got {n_pos!r}")
+    if isinstance(D, bool) or not isinstance(D, int) or D < 2 or D % 2:
+        raise ValueError(f"rope_table: D must be a positive even int, got {D!r}")
+    if inv_freq is None:
+        if not theta > 0:
+            raise ValueError(f"rope_table: theta must be positive, got {theta!r}")
+        inv_freq = torch.tensor([float(theta) ** (-2.0 * j / D) for j in range(D // 2)], dtype=torch.float64)
+    else:
+        if not isinstance(inv_freq, torch.Tensor) or inv_freq.dtype != torch.float64:
+            raise TypeError(f"rope_table: inv_freq must be a float64 tensor, got {getattr(inv_freq, 'dtype', type(inv_freq).__name__)}")
+        if tuple(inv_freq.shape) != (D // 2,):
+            raise ValueError(f"rope_table: inv_freq must be [D / 2 = {D // 2}], got {tuple(inv_freq.shape)}")
+        inv_freq = inv_freq.detach().cpu()
+    ang = torch.arange(n_pos, dtype=torch.float64)[:, None] * inv_freq[None, :]
+    table = torch.stack((torch.cos(ang), torch.sin(ang)), dim=1).to(torch.float32).contiguous()
+    return table if device is None else table.to(device)
+
+
+def _rope_same_or_apart(name: str, x, out) -> None:
+    """An output is its input (the same address AND strides: in place) or lies elsewhere."""
+    if out.data_ptr() == x.data_ptr() and out.stride() != x.stride():
+        raise ValueError(f"rope_apply: {name}_out starts at the address of {name} with other strides "
+                         f"({out.stride()} against {x.stride()}): in place means the same view")
+
+
+def rope_validate(q, k, table, pos0: int = 0, cu_seqlens=None, q_out=None, k_out=None):
+    """Argument rules of ``rope_apply`` / ``rope`` that need no GPU; raises TypeError (dtypes, those
+    of ``table`` and ``cu_seqlens`` included) / ValueError (everything else) and returns
+    ``(B, S, Hq, Hkv, D, P)`` -- ``B = 1``, ``S = T`` in the packed form, ``Hkv = 0`` without ``k``.
+
+    Batched (``cu_seqlens=None``): ``q`` [B, S, Hq, D], ``k`` [B, S, Hkv, D] or None; row ``s`` sits
+    at position ``pos0 + s``, ``pos0 >= 0`` and ``pos0 + S <= P``.  Packed: ``q`` [T, Hq, D], ``k``
+    [T, Hkv, D] or None, ``cu_seqlens`` a contiguous int32 [n + 1] tensor on the device of ``q``,
+    ``1 <= n <= 65536``, under the promises of ``flash_attention_varlen_validate`` (its contents are
+    read on the device only), ``pos0 = 0``.  ``q`` and ``k`` agree in every dimension but the heads,
+    which are independent.  All bf16 views: unit stride on D, every other stride a multiple of 8
+    elements, 16-byte-aligned base; ``D % 16 == 0``, ``16 <= D <= 256``.  ``table`` is a contiguous,
+    16-byte-aligned fp32 [P, 2, D / 2] tensor on that device.  ``q_out`` / ``k_out``: the shape,
+    dtype and device of their input under the same view rules, each with strides of its own; an
+    output may be its input (the same view).  Beyond that the caller promises what is not checked: an
+    output overlaps no operand other than the input it replaces, not in part and not at another
+    base address, and no output view overlaps itself (a stride of 0 on an axis longer than 1);
+    threads would race on such memory, at addresses inside the tensors.  ``tokens x D / 16 x
+    min(Hq + Hkv, 64)`` is at most ``256 x (2^31 - 1)`` (the grid)."""
+    pub = "rope_apply"
+    for name, t in (("q", q), ("k", k), ("q_out", q_out), ("k_out", k_out)):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.bfloat16):
+            raise TypeError(f"{pub} expects bf16 {name}, got {getattr(t, 'dtype', type(t).__name__)}")
+    if not isinstance(q, torch.Tensor):
+        raise TypeError(f"{pub} expects a bf16 tensor q, got {type(q).__name__}")
+    if not isinstance(table, torch.Tensor) or table.dtype != torch.float32:
+        raise TypeError(f"{pub}: table must be an fp32 tensor, got {getattr(table, 'dtype', type(table).__name__)}")
+    packed = cu_seqlens is not None
+    if packed and (not isinstance(cu_seqlens, torch.Tensor) or cu_seqlens.dtype != torch.int32):
+        raise TypeError(f"{pub}: cu_seqlens must be an int32 tensor, got "
+                        f"{getattr(cu_seqlens, 'dtype', type(cu_seqlens).__name__)}")
+    if isinstance(pos0, bool) or not isinstance(pos0, int):
+        raise ValueError(f"{pub}: pos0 must be an int, got {pos0!r}")
+    if k is None and k_out is not None:
+        raise ValueError(f"{pub}: k_out without k")
+    rank = 3 if packed else 4
+    form = "[T, H, D] (with cu_seqlens)" if packed else "[B, S, H, D] (with pos0)"
+    if q.dim() != rank:
+        raise ValueError(f"{pub}: q must be {form}, got {tuple(q.shape)}")
+    if packed:
+        if pos0 != 0:
+            raise ValueError(f"{pub}: cu_seqlens and a non-zero pos0 ({pos0}) exclude each other")
+        if cu_seqlens.dim() != 1 or cu_seqlens.shape[0] < 2 or not cu_seqlens.is_contiguous():
+            raise ValueError(f"{pub}: cu_seqlens must be a contiguous [n + 1] tensor with n >= 1, got shape "
+                             f"{tuple(cu_seqlens.shape)}, strides {cu_seqlens.stride()}")
+        if cu_seqlens.shape[0] - 1 > ROPE_MAX_SEQS:
+            raise ValueError(f"{pub}: at most {ROPE_MAX_SEQS} sequences, got {cu_seqlens.shape[0] - 1}")
+        if cu_seqlens.device != q.device:
+            raise ValueError(f"{pub}: cu_seqlens must be on the device of q ({q.device}), got {cu_seqlens.device}")
+    elif pos0 < 0:
+        raise ValueError(f"{pub}: pos0 must be >= 0, got {pos0}")
+    *lead, Hq, D = (int(x) for x in q.shape)
+    B, S = (1, lead[0]) if packed else lead
+    Hkv = 0
+    if k is not None:
+        if k.dim() != rank or tuple(k.shape[:-2]) != tuple(q.shape[:-2]) or k.shape[-1] != D:
+            raise ValueError(f"{pub}: k must agree with q {tuple(q.shape)} in every dimension but the heads, got "
+                             f"{tuple(k.shape)}")
+        Hkv = int(k.shape[-2])
+        if k.device != q.device:
+            raise ValueError(f"{pub}: q and k must be on one device")
+    if D < 16 or D > 256 or D % 16:
+        raise ValueError(f"{pub}: the head dim must be a multiple of 16 in [16, 256], got {D}")
+    if B < 1 or S < 1 or B * S > ROPE_MAX_TOKENS:
+        raise ValueError(f"{pub}: 1 <= tokens <= 2^30 required, got {tuple(q.shape)}")
+    if not (1 <= Hq <= ROPE_MAX_HEADS) or (k is not None and not (1 <= Hkv <= ROPE_MAX_HEADS)):
+        raise ValueError(f"{pub}: the heads must be in [1, {ROPE_MAX_HEADS}], got {Hq}" + (f" and {Hkv}" if k is not None else ""))
+    if B * S * (D // 16) * min(Hq + Hkv, ROPE_MAX_LANES) > ROPE_MAX_THREADS:
+        raise ValueError(f"{pub}: tokens x D / 16 x min(heads, {ROPE_MAX_LANES}) = {B * S} x {D // 16} x "
+                         f"{min(Hq + Hkv, ROPE_MAX_LANES)} exceeds the grid (256 x (2^31 - 1) threads)")
+    if table.dim() != 3 or table.shape[0] < 1 or tuple(table.shape[1:]) != (2, D // 2):
+        raise ValueError(f"{pub}: table must be [P, 2, D / 2 = {D // 2}], got {tuple(table.shape)}")
+    P = int(table.shape[0])
+    if P > ROPE_MAX_TOKENS:
+        raise ValueError(f"{pub}: at most 2^30 table rows, got {P}")
+    if not table.is_contiguous() or table.data_ptr() % 16:
+        raise ValueError(f"{pub}: table must be contiguous and start at a 16-byte-aligned address")
+    if table.device != q.device:
+        raise ValueError(f"{pub}: table must be on the device of q ({q.device}), got {table.device}")
+    if not packed and pos0 + S > P:
+        raise ValueError(f"{pub}: pos0 + S = {pos0} + {S} exceeds the table's {P} positions")
+    for name, x, out in (("q", q, q_out), ("k", k, k_out)):
+        if x is None:
+            continue
+        _flash_view_check(pub, name, x)
+        if out is not None:
+            if tuple(out.shape) != tuple(x.shape) or out.device != x.device:
+                raise ValueError(f"{pub}: {name}_out must be a {tuple(x.shape)} tensor on {x.device}, got "
+                                 f"{tuple(out.shape)} on {out.device}")
+            _flash_view_check(pub, name + "_out", out)
+            _rope_same_or_apart(name, x, out)
+    return B, S, Hq, Hkv, D, P
+
+
+def _rope_view(t):
+    """A view as the extension takes it: (address, batch, token, head stride) in elements; 0 for an
+    axis of length 1 and for the batch axis a packed [T, H, D] tensor does not have."""
+    st = [s if n > 1 else 0 for n, s in zip(t.shape[:-1], t.stride())]
+    return (t.data_ptr(), *[0] * (3 - len(st)), *st)
+
+
+def rope_apply(q, k, table, pos0: int = 0, cu_seqlens=None, interleaved: bool = False, inverse: bool = False,
+               q_out=None, k_out=None, *, _lanes: int = 0):
+    """Rotate ``q`` and, when given, ``k`` by their positions' angles in ONE launch; returns
+    ``(q_out, k_out)``, ``(q_out, None)`` for ``k=None``.  Operands as ``rope_validate`` describes.
+
+    Each pair ``(x1, x2)`` of a head becomes ``(x1 c - x2 s, x2 c + x1 s)`` with ``c`` / ``s`` the
+    table's cos / sin of (position, frequency ``j``): the pair is ``(x[j], x[j + D/2])`` (half-split,
+    the layout of Hugging Face Llama checkpoints) or, ``interleaved=True``, ``(x[2j], x[2j + 1])``
+    (Meta's original layout).  fp32 arithmetic, one rounding to bf16.  ``inverse=True`` uses ``-s``:
+    the transpose of the rotation, i.e. its backward.  The position of a row is ``pos0 + s``
+    (``pos0 = r S_loc`` on rank ``r`` of a context-parallel group), or with ``cu_seqlens`` the
+    token's index inside its document, the boundaries read -- and clamped as in
+    ``flash_attention_varlen`` -- on the device; rows from ``cu_seqlens[n]`` on are not written.  The
+    table row is clamped to ``P - 1`` on the device: a packed document longer than ``P`` gives
+    unspecified values at safe addresses.
+
+    With every output passed the call allocates nothing and never synchronises with the host, so
+    it can be captured in a graph, and a replay follows the contents of ``cu_seqlens``.  An output
+    may be its input.  Outputs the call allocates are contiguous.  ``v`` is none of its business.
+    ``_lanes`` is private (the benchmark's sweep and one test): it overrides how the heads are dealt
+    to a token's threads, 0 = the kernel's own choice; the results are bitwise the same for every value."""
+    B, S, Hq, Hkv, D, P = rope_validate(q, k, table, pos0, cu_seqlens, q_out, k_out)
+    if q_out is None:
+        q_out = torch.empty(q.shape, dtype=torch.bfloat16, device=q.device)
+    if k is not None and k_out is None:
+        k_out = torch.empty(k.shape, dtype=torch.bfloat16, device=k.device)
+    none = (0, 0, 0, 0)
+    _D().rope_apply(_rope_view(q), _rope_view(q_out), Hq, none if k is None else _rope_view(k),
+                    none if k is None else _rope_view(k_out), Hkv, table.data_ptr(), P, B, S, D, int(pos0),
+                    *_flash_packing(cu_seqlens), bool(interleaved), bool(inverse), int(_lanes), _stream(q))
+    return q_out, k_out
+
+
+class _Rope(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, table, pos0, cu_seqlens, interleaved):
+        ctx.save_for_backward(table)
+        ctx.cu_seqlens = cu_seqlens  # an index tensor, no gradient: the backward reads it as it is then
+        ctx.args = (pos0, interleaved, k is not None)
+        q_out, k_out = rope_apply(q, k, table, pos0, cu_seqlens, interleaved)
+        return q_out, k_out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dq, dk):
+        (table,) = ctx.saved_tensors
+        pos0, interleaved, has_k = ctx.args
+        dq = dq if flash_is_view(dq) else dq.contiguous()
+        if has_k:
+            dk = dk if flash_is_view(dk) else dk.contiguous()
+        dq, dk = rope_apply(dq, dk if has_k else None, table, pos0, ctx.cu_seqlens, interleaved, inverse=True)
+        return dq, dk, None, None, None, None
+
+
+def rope(q, k, table, pos0: int = 0, cu_seqlens=None, interleaved: bool = False):
+    """Differentiable ``rope_apply``, out of place: ``(q_out, k_out)`` contiguous bf16,
+    differentiable in ``q`` and ``k`` (``k`` may be None).  The backward is one
+    ``rope_apply(..., inverse=True)`` launch on the incoming gradients (made contiguous when they
+    do not follow the view rules).  In the packed form rows from ``cu_seqlens[n]`` on are left
+    unwritten, and their gradients too."""
+    rope_validate(q, k, table, pos0, cu_seqlens)
+    return _Rope.apply(q, k, table, int(pos0), cu_seqlens, bool(interleaved))
+
+
+def rope_reference(x, table, positions, interleaved: bool = False, inverse: bool = False):
+    """The rotation in torch fp64 (any device), before any rounding: ``x`` [..., H, D],
+    ``positions`` an int64 tensor over the token axes ``x.shape[:-2]``, ``table`` [P, 2, D / 2].
+    Pair ``j`` of a head -- ``(x[j], x[j + D/2])``, interleaved ``(x[2j], x[2j + 1])`` -- becomes
+    ``(x1 c - x2 s, x2 c + x1 s)`` with ``c, s = table[position, 0 / 1, j]`` (``-s`` for
+    ``inverse``)."""
+    x = x.double()
+    D = x.shape[-1]
+    if positions.dtype != torch.int64 or tuple(positions.shape) != tuple(x.shape[:-2]):
+        raise ValueError(f"rope_reference: positions must be int64 {tuple(x.shape[:-2])}, got {positions.dtype} "
+                         f"{tuple(positions.shape)}")
+    rows = table.double()[positions.to(table.device)].to(x.device)  # [..., 2, D / 2]
+    c, s = rows[..., 0, :].unsqueeze(-2), rows[..., 1, :].unsqueeze(-2)
+    if inverse:
+        s = -s
+    x1, x2 = (x[..., 0::2], x[..., 1::2]) if interleaved else (x[..., : D // 2], x[..., D // 2:])
+    y1, y2 = x1 * c - x2 * s, x2 * c + x1 * s
+    if interleaved:
+        return torch.stack((y1, y2), dim=-1).reshape(x.shape)
+    return torch.cat((y1, y2), dim=-1)

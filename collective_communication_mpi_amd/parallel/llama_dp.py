@@ -40,8 +40,17 @@ a vocabulary NEEDS "fused": ``F.cross_entropy`` on a ``vocab / p``-wide shard wi
 never computed a loss (it indexed past the shard), so that combination is refused at construction.
 Under TP the block's attention runs on this rank's ``heads / p`` query and ``kv_heads / p`` key /
 value heads (``p`` must divide both).
-RoPE is left out (no effect on gradient sizes or the GEMM work).  Random-init weights,
-synthetic token ids.
+Positions: by default RoPE is left out (no effect on gradient sizes or the GEMM work) and the
+model has no notion of position beyond the causal mask.  ``LlamaConfig.rope = True`` rotates q and k
+(never v) right after the projections, on their [.., H, hd] views, with the project's own kernel
+(``ops.rope``, csrc/device/rope.hip) in all four attention paths: "sdpa" (before the transposes),
+"flash", "flash" with ``cp`` (row ``s`` of rank ``r`` sits at position ``r * seq + s``) and "flash"
+with ``cu_seqlens`` (a token's position is its index inside its document, the boundaries read on
+the device).  The model builds one cos / sin table of ``max_positions`` rows (``ops.rope_table``,
+``rope_theta``) and shares it with its blocks; a sequence -- under ``cp`` the whole one, ``cp_size *
+seq`` -- longer than that raises before any launch (a packed document longer than it is the
+caller's to avoid).  With ``rope = False`` the forward never enters that code.  Random-init
+weights, synthetic token ids.
 """
 from __future__ import annotations
 
@@ -52,7 +61,7 @@ from typing import Dict, List, Optional
 import torch
 import torch.nn.functional as F
 
-from ..ops.kernels import FLASH_HEAD_DIMS, flash_attention, flash_attention_varlen
+from ..ops.kernels import FLASH_HEAD_DIMS, flash_attention, flash_attention_varlen, rope, rope_table
 from .context_parallel import context_parallel_attention
 from .ddp import DistributedDataParallel
 from .tensor_parallel import ColumnParallelLinear, ParallelSwiGLUMLP, RowParallelLinear, _size_rank
@@ -70,6 +79,9 @@ class LlamaConfig:
     eps: float = 1e-5
     attention: str = "sdpa"  # "sdpa" (PyTorch) or "flash" (ops.flash_attention, head dim 64 / 128)
     loss: str = "torch"  # "torch" (F.cross_entropy on fp32 logits) or "fused" (vocab_parallel_cross_entropy)
+    rope: bool = False  # rotate q and k by their positions (ops.rope); False: no notion of position
+    rope_theta: float = 500000.0
+    max_positions: int = 8192  # rows of the cos / sin table: the longest sequence rope=True accepts
 
     @property
     def head_dim(self) -> int:
@@ -96,12 +108,27 @@ class RMSNorm(torch.nn.Module):
         return F.rms_norm(x, (x.shape[-1],), self.weight, self.eps)
 
 
+def _check_rope_config(cfg: LlamaConfig) -> None:
+    if not cfg.rope:
+        return
+    if cfg.head_dim % 16 or not 16 <= cfg.head_dim <= 256:
+        raise ValueError(f"rope=True needs a head dim that is a multiple of 16 in [16, 256], got {cfg.head_dim}")
+    if isinstance(cfg.max_positions, bool) or not isinstance(cfg.max_positions, int) or cfg.max_positions < 1:
+        raise ValueError(f"LlamaConfig.max_positions must be a positive int, got {cfg.max_positions!r}")
+    if not cfg.rope_theta > 0:
+        raise ValueError(f"LlamaConfig.rope_theta must be positive, got {cfg.rope_theta!r}")
+
+
 class LlamaBlock(torch.nn.Module):
-    def __init__(self, cfg: LlamaConfig, tp, seed: int, device, dtype=torch.bfloat16, cp=None):
+    def __init__(self, cfg: LlamaConfig, tp, seed: int, device, dtype=torch.bfloat16, cp=None, rope_table=None):
         super().__init__()
         d, kv = cfg.d, cfg.kv_heads * cfg.head_dim
         self.cfg = cfg
         self.cp = cp  # context-parallel communicator: x holds this rank's shard of the sequence
+        _check_rope_config(cfg)
+        if cfg.rope and rope_table is None:
+            raise ValueError("LlamaConfig.rope needs the model's cos / sin table (rope_table)")
+        self.rope_table = rope_table if cfg.rope else None  # shared by every block: a plain attribute, no buffer
         if cfg.attention not in ATTENTION_KINDS:
             raise ValueError(f"LlamaConfig.attention must be one of {ATTENTION_KINDS}, got {cfg.attention!r}")
         if cfg.attention == "flash" and cfg.head_dim not in FLASH_HEAD_DIMS:
@@ -112,6 +139,7 @@ class LlamaBlock(torch.nn.Module):
         if cfg.heads % p or cfg.kv_heads % p:
             raise ValueError(f"the TP size {p} must divide heads ({cfg.heads}) and kv_heads ({cfg.kv_heads})")
         self.heads, self.kv_heads = cfg.heads // p, cfg.kv_heads // p  # this rank's heads
+        self.cp_size, self.cp_rank = _size_rank(cp) if cfg.rope and cp is not None else (1, 0)
         kw = dict(bias=False, device=device, dtype=dtype, init="device")
         self.attn_norm = RMSNorm(d, cfg.eps, device, dtype)
         self.wq = ColumnParallelLinear(d, d, tp, seed=seed, **kw)
@@ -121,30 +149,45 @@ class LlamaBlock(torch.nn.Module):
         self.mlp_norm = RMSNorm(d, cfg.eps, device, dtype)
         self.mlp = ParallelSwiGLUMLP(d, cfg.ffn, tp, device=device, dtype=dtype, seed=seed + 4, init="device")
 
+    def check_positions(self, seq: int, cu_seqlens=None) -> None:
+        """rope: the whole sequence (``cp_size * seq``) fits the table.  Packed documents are not
+        checked: their lengths live on the device (the kernel clamps the table row)."""
+        cfg = self.cfg
+        if cfg.rope and cu_seqlens is None and self.cp_size * seq > cfg.max_positions:
+            raise ValueError(f"rope: {self.cp_size} x {seq} positions exceed LlamaConfig.max_positions = "
+                             f"{cfg.max_positions}")
+
     def forward(self, x, batch: int, seq: int, cu_seqlens: Optional[torch.Tensor] = None):
         cfg = self.cfg
         hd, hq, hkv = cfg.head_dim, self.heads, self.kv_heads
+        self.check_positions(seq, cu_seqlens)  # before any launch of this block
         if cu_seqlens is not None:  # packed documents: boundaries on the flattened batch * seq token axis
             if cfg.attention != "flash" or self.cp is not None:
                 raise ValueError('cu_seqlens needs attention="flash" and no context parallelism (cp), got '
                                  f"attention={cfg.attention!r}, cp {'set' if self.cp is not None else 'None'}")
             n = self.attn_norm(x)
-            o = flash_attention_varlen(self.wq(n).view(batch * seq, hq, hd), self.wk(n).view(batch * seq, hkv, hd),
-                                       self.wv(n).view(batch * seq, hkv, hd), cu_seqlens, causal=True)
+            q, k = self.wq(n).view(batch * seq, hq, hd), self.wk(n).view(batch * seq, hkv, hd)
+            if cfg.rope:  # a token's position is its index inside its document
+                q, k = rope(q, k, self.rope_table, cu_seqlens=cu_seqlens)
+            o = flash_attention_varlen(q, k, self.wv(n).view(batch * seq, hkv, hd), cu_seqlens, causal=True)
             h = x + self.wo(o.view(batch * seq, hq * hd))
             return h + self.mlp(self.mlp_norm(h))
         n = self.attn_norm(x)
         if cfg.attention == "flash":  # the projections' views as they are; K and V stay at kv_heads
             q, k, v = (self.wq(n).view(batch, seq, hq, hd), self.wk(n).view(batch, seq, hkv, hd),
                        self.wv(n).view(batch, seq, hkv, hd))
+            if cfg.rope:  # under cp this rank's rows start at position cp_rank * seq
+                q, k = rope(q, k, self.rope_table, pos0=self.cp_rank * seq)
             if self.cp is not None:  # seq is this rank's shard; K | V of the other shards are gathered
                 o = context_parallel_attention(self.cp, q, k, v, causal=True)
             else:
                 o = flash_attention(q, k, v, causal=True)
             h = x + self.wo(o.view(batch * seq, hq * hd))
             return h + self.mlp(self.mlp_norm(h))
-        q = self.wq(n).view(batch, seq, hq, hd).transpose(1, 2)
-        k = self.wk(n).view(batch, seq, hkv, hd).transpose(1, 2)
+        q, k = self.wq(n).view(batch, seq, hq, hd), self.wk(n).view(batch, seq, hkv, hd)
+        if cfg.rope:
+            q, k = rope(q, k, self.rope_table)
+        q, k = q.transpose(1, 2), k.transpose(1, 2)
         v = self.wv(n).view(batch, seq, hkv, hd).transpose(1, 2)
         rep = hq // hkv
         if rep > 1:  # GQA: expand the kv heads (keeps SDPA on its fused path)
@@ -170,6 +213,7 @@ class LlamaModel(torch.nn.Module):
         self.cfg = cfg
         self.vocab = vocab
         self.tp = tp
+        _check_rope_config(cfg)
         if cfg.loss not in LOSS_KINDS:
             raise ValueError(f"LlamaConfig.loss must be one of {LOSS_KINDS}, got {cfg.loss!r}")
         if vocab and cfg.loss == "torch" and _size_rank(tp)[0] > 1:
@@ -180,7 +224,10 @@ class LlamaModel(torch.nn.Module):
             with torch.no_grad():
                 g = torch.Generator(device=device).manual_seed(seed)
                 self.embed.weight.normal_(0.0, 0.02, generator=g)
-        self.blocks = torch.nn.ModuleList(LlamaBlock(cfg, tp, seed + 10 * (i + 1), device, dtype, cp=cp)
+        # one cos / sin table for every block (fp32 [max_positions, 2, head_dim / 2]); None without rope
+        self.rope_table = rope_table(cfg.max_positions, cfg.head_dim, cfg.rope_theta, device=device) if cfg.rope else None
+        self.blocks = torch.nn.ModuleList(LlamaBlock(cfg, tp, seed + 10 * (i + 1), device, dtype, cp=cp,
+                                                     rope_table=self.rope_table)
                                           for i in range(cfg.layers))
         self.norm = RMSNorm(cfg.d, cfg.eps, device, dtype)
         if vocab:
@@ -190,6 +237,8 @@ class LlamaModel(torch.nn.Module):
     def forward(self, ids, x0: Optional[torch.Tensor] = None, targets: Optional[torch.Tensor] = None,
                 cu_seqlens: Optional[torch.Tensor] = None):
         b, s = ids.shape
+        for blk in self.blocks[:1]:  # a sequence beyond max_positions is refused before the embedding runs
+            blk.check_positions(s, cu_seqlens)
         x = self.embed(ids).view(b * s, self.cfg.d) if self.vocab else x0
         for blk in self.blocks:
             x = blk(x, b, s, cu_seqlens)
