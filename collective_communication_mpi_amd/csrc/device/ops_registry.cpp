@@ -16,6 +16,7 @@ void register_moe_router_ops(pybind11::module_& m);
 void register_flash_attn_ops(pybind11::module_& m);
 void register_xent_ops(pybind11::module_& m);
 void register_rope_ops(pybind11::module_& m);
+void register_rmsnorm_ops(pybind11::module_& m);
 
 void register_ops(pybind11::module_& m) {
   register_layout_ops(m);
@@ -30,6 +31,7 @@ void register_ops(pybind11::module_& m) {
   register_flash_attn_ops(m);
   register_xent_ops(m);
   register_rope_ops(m);
+  register_rmsnorm_ops(m);
 }
 
 }  // namespace dev

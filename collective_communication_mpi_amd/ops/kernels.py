@@ -1874,3 +1874,265 @@ def rope_reference(x, table, positions, interleaved: bool = False, inverse: bool
     if interleaved:
         return torch.stack((y1, y2), dim=-1).reshape(x.shape)
     return torch.cat((y1, y2), dim=-1)
+
+
+# ---------------------------------------------------------------------------
+# RMSNorm with the residual add in front of it (csrc/device/rmsnorm.hip)
+# ---------------------------------------------------------------------------
+RMS_NORM_MAX_D = 16384      # csrc/device/rmsnorm.hpp kRmsMaxD
+RMS_NORM_MAX_ROWS = 1 << 30  # kRmsMaxRows
+_RMS_MIN_CHUNK = 8          # kRmsMinChunk
+_RMS_MAX_CHUNK = 32         # kRmsMaxChunk
+_RMS_TARGET_GROUPS = 1024   # kRmsTargetGroups
+
+
+def rms_norm_row_chunk(T: int, d: int) -> int:
+    """Rows per workgroup of ``rms_norm_backward``: ``clamp(ceil(T / 1024), 8, 32)``, a pure
+    function of ``(T, d)`` (the mirror of csrc/device/rmsnorm.hpp, which the launcher checks) and
+    never of the device or the grid.  A chunk's rows are added into its ``dw`` partial in row
+    order and the partials in a fixed order, so the rule is part of ``dw``'s bits; ``partials`` is
+    ``[ceil(T / chunk), d]`` fp32."""
+    T, d = int(T), int(d)
+    if T < 1 or d < 1:
+        raise ValueError(f"rms_norm_row_chunk: T and d must be positive, got {T}, {d}")
+    return max(_RMS_MIN_CHUNK, min(_RMS_MAX_CHUNK, (T + _RMS_TARGET_GROUPS - 1) // _RMS_TARGET_GROUPS))
+
+
+def _rms_rows_rules(name: str, t, shape=None, device=None) -> None:
+    """[T, d] bf16, unit column stride, row stride a multiple of 8, 16-byte-aligned base."""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.bfloat16:
+        raise TypeError(f"rms_norm expects bf16 {name}, got {getattr(t, 'dtype', type(t).__name__)}")
+    if t.dim() != 2:
+        raise ValueError(f"rms_norm: {name} must be [T, d], got {tuple(t.shape)}")
+    T, d = (int(n) for n in t.shape)
+    if shape is not None and (T, d) != tuple(shape):
+        raise ValueError(f"rms_norm: {name} must be {tuple(shape)}, got {(T, d)}")
+    if d < 8 or d > RMS_NORM_MAX_D or d % 8:
+        raise ValueError(f"rms_norm: d must be a multiple of 8 in [8, {RMS_NORM_MAX_D}], got {d}")
+    if T < 1 or T > RMS_NORM_MAX_ROWS:
+        raise ValueError(f"rms_norm: 1 <= T <= 2^30 required, got {T}")
+    if t.stride(1) != 1:
+        raise ValueError(f"rms_norm: {name} must have unit column stride, got {t.stride(1)}")
+    if T > 1 and t.stride(0) % 8:
+        raise ValueError(f"rms_norm: the row stride of {name} must be a multiple of 8 elements, got {t.stride(0)}")
+    if t.data_ptr() % 16:
+        raise ValueError(f"rms_norm: {name} must start at a 16-byte-aligned address")
+    if device is not None and t.device != device:
+        raise ValueError(f"rms_norm: {name} is on {t.device}, expected {device}")
+
+
+def _rms_weight_rules(weight, d: int, device) -> None:
+    if not isinstance(weight, torch.Tensor) or weight.dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError(f"rms_norm expects a bf16 or fp32 weight, got {getattr(weight, 'dtype', type(weight).__name__)}")
+    if tuple(weight.shape) != (d,) or not weight.is_contiguous():
+        raise ValueError(f"rms_norm: weight must be a contiguous [{d}] tensor, got shape {tuple(weight.shape)}, strides "
+                         f"{weight.stride()}")
+    if weight.data_ptr() % 16:
+        raise ValueError("rms_norm: weight must start at a 16-byte-aligned address")
+    if weight.device != device:
+        raise ValueError(f"rms_norm: weight is on {weight.device}, expected {device}")
+
+
+def _rms_same_or_apart(name: str, out, *inputs) -> None:
+    """An output is an input (the same address AND strides: in place) or lies elsewhere."""
+    for x in inputs:
+        if x is not None and out.data_ptr() == x.data_ptr() and out.shape[0] > 1 and out.stride() != x.stride():
+            raise ValueError(f"rms_norm: {name} starts at the address of an operand with other strides "
+                             f"({out.stride()} against {x.stride()}): in place means the same view")
+
+
+def rms_norm_validate(x, weight, residual=None, eps: float = 1e-5, h=None, y=None):
+    """Argument rules of the RMSNorm forward ops that need no GPU; raises TypeError (dtypes) /
+    ValueError (the rest) and returns ``(T, d)``.  ``x``, ``residual``, ``h``, ``y`` are [T, d]
+    bf16 views of one shape on one device: unit column stride, a row stride that is a multiple of
+    8 elements (each its own: a row view or a column slice of a larger buffer qualifies), a
+    16-byte-aligned base; ``8 <= d <= 16384``, ``d % 8 == 0``, ``1 <= T <= 2^30``.  ``weight`` is
+    [d] bf16 or fp32, contiguous, 16-byte aligned; ``eps`` a positive host float.  ``h`` needs
+    ``residual`` and may BE ``x`` or ``residual`` (the same view).  The caller promises what is not
+    checked: no output overlaps an operand in any other way, and no output view overlaps itself."""
+    _rms_rows_rules("x", x)
+    T, d = (int(n) for n in x.shape)
+    if residual is not None:
+        _rms_rows_rules("residual", residual, (T, d), x.device)
+    _rms_weight_rules(weight, d, x.device)
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not eps > 0 or eps == float("inf") \
+            or not torch.tensor(float(eps), dtype=torch.float32).item() > 0:
+        raise ValueError(f"rms_norm: eps must be a positive float, got {eps!r}")
+    if h is not None:
+        if residual is None:
+            raise ValueError("rms_norm: h without residual")
+        _rms_rows_rules("h", h, (T, d), x.device)
+        _rms_same_or_apart("h", h, x, residual)
+    if y is not None:
+        _rms_rows_rules("y", y, (T, d), x.device)
+    return T, d
+
+
+def _rms_view(t):
+    """A view as the extension takes it: (address, row stride in elements; 0 for one row)."""
+    return (0, 0) if t is None else (t.data_ptr(), t.stride(0) if t.shape[0] > 1 else 0)
+
+
+def _rms_buffer(name: str, t, shape, device, align: int):
+    """A caller's fp32 buffer (exact shape, contiguous, on ``device``) or a fresh one."""
+    if t is None:
+        return torch.empty(shape, dtype=torch.float32, device=device)
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+        raise TypeError(f"rms_norm: {name} must be fp32, got {getattr(t, 'dtype', type(t).__name__)}")
+    if tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"rms_norm: {name} must be a contiguous {tuple(shape)} tensor, got {tuple(t.shape)}")
+    if t.device != device:
+        raise ValueError(f"rms_norm: {name} is on {t.device}, expected {device}")
+    if t.data_ptr() % align:
+        raise ValueError(f"rms_norm: {name} must start at a {align}-byte-aligned address")
+    return t
+
+
+def add_rms_norm_forward(x, residual, weight, eps: float, h=None, y=None, rstd=None):
+    """``h = bf16(x + residual)`` -- one fp32 add, rounded once: the bits of torch's bf16 ``x +
+    residual`` -- then, of the ROUNDED ``h``: ``rstd[t] = 1 / sqrt(mean_j h[t, j]^2 + eps)`` (fp32
+    [T]) and ``y[t, j] = bf16(h[t, j] * rstd[t] * weight[j])`` (products in fp32, one rounding), in
+    ONE launch (``k_rmsnorm_fwd``): each row is read once, kept in registers and written once
+    (twice: ``h`` and ``y``).  Returns ``(h, y, rstd)``.  Operands as ``rms_norm_validate``
+    describes; ``h`` may be ``x`` or ``residual``.  A row's results depend on that row and ``d``
+    alone, never on ``T`` or the other rows.  With ``h``, ``y`` and ``rstd`` passed the call
+    allocates nothing and never synchronises with the host; outputs it allocates are contiguous."""
+    if residual is None:
+        raise ValueError("rms_norm: add_rms_norm_forward needs a residual (rms_norm_forward takes none)")
+    T, d = rms_norm_validate(x, weight, residual, eps, h, y)
+    rstd = _rms_buffer("rstd", rstd, (T,), x.device, 4)
+    if h is None:
+        h = torch.empty((T, d), dtype=torch.bfloat16, device=x.device)
+    if y is None:
+        y = torch.empty((T, d), dtype=torch.bfloat16, device=x.device)
+    _D().rms_norm_fwd(_rms_view(x), _rms_view(residual), _rms_view(h), _rms_view(y), weight.data_ptr(),
+                      weight.dtype == torch.float32, rstd.data_ptr(), T, d, float(eps), _stream(x))
+    return h, y, rstd
+
+
+def rms_norm_forward(x, weight, eps: float, y=None, rstd=None):
+    """``add_rms_norm_forward`` without a residual (``h`` is ``x``): returns ``(y, rstd)``."""
+    T, d = rms_norm_validate(x, weight, None, eps, None, y)
+    rstd = _rms_buffer("rstd", rstd, (T,), x.device, 4)
+    if y is None:
+        y = torch.empty((T, d), dtype=torch.bfloat16, device=x.device)
+    _D().rms_norm_fwd(_rms_view(x), (0, 0), (0, 0), _rms_view(y), weight.data_ptr(), weight.dtype == torch.float32,
+                      rstd.data_ptr(), T, d, float(eps), _stream(x))
+    return y, rstd
+
+
+def rms_norm_backward(dy, h, weight, rstd, dres=None, dh=None, dw=None, partials=None, need_dw: bool = True):
+    """With ``n = h * rstd`` and ``g = dy * weight``: ``dh[t, j] = bf16(rstd[t] * (g[t, j] - n[t, j]
+    * mean_k(g[t, k] n[t, k])) + dres[t, j])``, rounded once, and ``dw[j] = sum_t dy[t, j] *
+    n[t, j]`` in fp32 ([d], whatever the weight's dtype).  ``dres`` is the gradient that reaches
+    ``h`` through the residual stream (None: zeros, bit for bit).  Returns ``(dh, dw)``.
+
+    ``dy``, ``h``, ``dres``, ``dh`` are [T, d] bf16 views under the rules of ``rms_norm_validate``;
+    ``dh`` may BE ``dy`` or ``dres``.  ``rstd`` is the forward's [T] fp32.  ``k_rmsnorm_bwd`` gives a
+    workgroup ``rms_norm_row_chunk(T, d)`` consecutive rows and writes their column sums, added in
+    row order, into ``partials`` (fp32 ``[ceil(T / chunk), d]``); ``k_rmsnorm_dw`` adds the partials
+    in a fixed order.  No atomics: ``dw`` is bitwise reproducible and does not depend on the
+    device.  ``need_dw=False`` skips both (``dw`` and ``partials`` are not touched; ``(dh, None)``).
+    With ``dh``, ``dw`` and ``partials`` passed the call allocates nothing and never synchronises."""
+    _rms_rows_rules("dy", dy)
+    T, d = (int(n) for n in dy.shape)
+    dev = dy.device
+    _rms_rows_rules("h", h, (T, d), dev)
+    if dres is not None:
+        _rms_rows_rules("dres", dres, (T, d), dev)
+    _rms_weight_rules(weight, d, dev)
+    if rstd is None:
+        raise ValueError("rms_norm: rms_norm_backward needs the forward's rstd")
+    rstd = _rms_buffer("rstd", rstd, (T,), dev, 4)
+    if dh is not None:
+        _rms_rows_rules("dh", dh, (T, d), dev)
+        _rms_same_or_apart("dh", dh, dy, dres)
+    chunk = rms_norm_row_chunk(T, d)
+    if need_dw:
+        dw = _rms_buffer("dw", dw, (d,), dev, 4)
+        partials = _rms_buffer("partials", partials, ((T + chunk - 1) // chunk, d), dev, 16)
+    if dh is None:
+        dh = torch.empty((T, d), dtype=torch.bfloat16, device=dev)
+    _D().rms_norm_bwd(_rms_view(dy), _rms_view(h), _rms_view(dres), _rms_view(dh), weight.data_ptr(),
+                      weight.dtype == torch.float32, rstd.data_ptr(), partials.data_ptr() if need_dw else 0,
+                      dw.data_ptr() if need_dw else 0, T, d, chunk, _stream(dy))
+    return dh, (dw if need_dw else None)
+
+
+def _rms_grad_rows(g):
+    """An incoming gradient as the kernel reads it (made contiguous when it breaks the view
+    rules, e.g. the expanded scalar of a sum); None stays None."""
+    if g is None:
+        return None
+    ok = g.dim() == 2 and g.stride(1) == 1 and (g.shape[0] == 1 or g.stride(0) % 8 == 0) and g.data_ptr() % 16 == 0
+    return g if ok else g.contiguous()
+
+
+class _AddRMSNorm(torch.autograd.Function):
+    """(x, residual or None, weight) -> (h, y); without a residual h is x and only y is returned."""
+
+    @staticmethod
+    def forward(ctx, x, residual, weight, eps):
+        if residual is None:
+            y, rstd = rms_norm_forward(x, weight, eps)
+            h = x
+        else:
+            h, y, rstd = add_rms_norm_forward(x, residual, weight, eps)
+        ctx.save_for_backward(h, weight, rstd)  # never y
+        ctx.has_residual = residual is not None
+        ctx.need_dw = weight.requires_grad
+        return (h, y) if residual is not None else y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        h, weight, rstd = ctx.saved_tensors
+        dres, dy = grads if ctx.has_residual else (None, grads[0])
+        dy = torch.zeros_like(h) if dy is None else _rms_grad_rows(dy)  # no dy: zeros for the norm path and dw
+        dh, dw = rms_norm_backward(dy, h, weight, rstd, _rms_grad_rows(dres), need_dw=ctx.need_dw)
+        if dw is not None:
+            dw = dw.to(weight.dtype)
+        return (dh if ctx.needs_input_grad[0] else None, dh if ctx.has_residual and ctx.needs_input_grad[1] else None,
+                dw, None)
+
+
+def rms_norm(x, weight, eps: float):
+    """Differentiable ``rms_norm_forward``: ``y`` [T, d] bf16, contiguous, differentiable in ``x``
+    and ``weight``.  Saves ``x``, ``weight`` and ``rstd``, never ``y``; the backward is one
+    ``rms_norm_backward`` launch and returns ``dw`` cast to the weight's dtype."""
+    rms_norm_validate(x, weight, None, eps)
+    return _AddRMSNorm.apply(x, None, weight, float(eps))
+
+
+def add_rms_norm(x, residual, weight, eps: float):
+    """Differentiable ``add_rms_norm_forward``: ``(h, y)``, both differentiable, in ``x``,
+    ``residual`` and ``weight``.  The backward receives the gradients of both outputs (either may
+    be missing), makes ONE ``rms_norm_backward`` launch with the gradient of ``h`` as ``dres``,
+    and returns the same ``dh`` tensor for ``x`` and for ``residual`` and ``dw`` cast to the
+    weight's dtype.  Saves ``h``, ``weight`` and ``rstd``, never ``y``."""
+    rms_norm_validate(x, weight, residual, eps)
+    return _AddRMSNorm.apply(x, residual, weight, float(eps))
+
+
+def rms_norm_reference(x, weight, eps: float, residual=None):
+    """The forward in torch fp64 (any device), written from the formulas: returns ``(h, y, rstd)``
+    with ``h = bf16(x + residual)`` (torch's own bf16 add; ``x`` without a residual), ``rstd = 1 /
+    sqrt(mean_j h^2 + eps)`` and ``y = h * rstd * weight`` before its rounding, both fp64."""
+    h = x if residual is None else x + residual
+    hd = h.double()
+    rstd = 1.0 / torch.sqrt((hd * hd).mean(dim=-1) + float(eps))
+    return h, hd * rstd[:, None] * weight.double()[None, :], rstd
+
+
+def rms_norm_backward_reference(dy, h, weight, eps: float, dres=None):
+    """The backward in torch fp64 (any device): ``(dh, dw)`` before any rounding, ``rstd``
+    recomputed from ``h`` in fp64: ``n = h * rstd``, ``g = dy * weight``, ``dh = rstd * (g - n *
+    mean_k(g n)) + dres``, ``dw = sum_t dy * n``."""
+    hd, dyd = h.double(), dy.double()
+    rstd = 1.0 / torch.sqrt((hd * hd).mean(dim=-1, keepdim=True) + float(eps))
+    n = hd * rstd
+    g = dyd * weight.double()[None, :]
+    dh = rstd * (g - n * (g * n).mean(dim=-1, keepdim=True))
+    if dres is not None:
+        dh = dh + dres.double()
+    return dh, (dyd * n).sum(dim=0)

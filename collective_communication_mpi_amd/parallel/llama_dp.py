@@ -49,8 +49,13 @@ with ``cu_seqlens`` (a token's position is its index inside its document, the bo
 the device).  The model builds one cos / sin table of ``max_positions`` rows (``ops.rope_table``,
 ``rope_theta``) and shares it with its blocks; a sequence -- under ``cp`` the whole one, ``cp_size *
 seq`` -- longer than that raises before any launch (a packed document longer than it is the
-caller's to avoid).  With ``rope = False`` the forward never enters that code.  Random-init
-weights, synthetic token ids.
+caller's to avoid).  With ``rope = False`` the forward never enters that code.
+Norms: ``LlamaConfig.norm = "torch"`` (the default) is ``F.rms_norm`` and plain ``x + ...`` adds;
+"fused" is the project's own kernel family (``ops.rms_norm`` / ``ops.add_rms_norm``,
+csrc/device/rmsnorm.hip) in all four attention paths: every residual add is computed by the norm
+that follows it (a block hands its MLP output on as a pending addend, which the next block's
+``attn_norm`` or the model's final ``norm`` adds), and the norm weights' gradients are summed in a
+fixed order.  Random-init weights, synthetic token ids.
 """
 from __future__ import annotations
 
@@ -61,7 +66,8 @@ from typing import Dict, List, Optional
 import torch
 import torch.nn.functional as F
 
-from ..ops.kernels import FLASH_HEAD_DIMS, flash_attention, flash_attention_varlen, rope, rope_table
+from ..ops.kernels import (FLASH_HEAD_DIMS, RMS_NORM_MAX_D, add_rms_norm, flash_attention, flash_attention_varlen,
+                           rms_norm, rope, rope_table)
 from .context_parallel import context_parallel_attention
 from .ddp import DistributedDataParallel
 from .tensor_parallel import ColumnParallelLinear, ParallelSwiGLUMLP, RowParallelLinear, _size_rank
@@ -82,6 +88,7 @@ class LlamaConfig:
     rope: bool = False  # rotate q and k by their positions (ops.rope); False: no notion of position
     rope_theta: float = 500000.0
     max_positions: int = 8192  # rows of the cos / sin table: the longest sequence rope=True accepts
+    norm: str = "torch"  # "torch" (F.rms_norm, x + ... adds) or "fused" (ops.rms_norm / ops.add_rms_norm)
 
     @property
     def head_dim(self) -> int:
@@ -96,6 +103,7 @@ class LlamaConfig:
 LLAMA3_8B = LlamaConfig()
 ATTENTION_KINDS = ("sdpa", "flash")
 LOSS_KINDS = ("torch", "fused")
+NORM_KINDS = ("torch", "fused")
 
 
 class RMSNorm(torch.nn.Module):
@@ -119,6 +127,13 @@ def _check_rope_config(cfg: LlamaConfig) -> None:
         raise ValueError(f"LlamaConfig.rope_theta must be positive, got {cfg.rope_theta!r}")
 
 
+def _check_norm_config(cfg: LlamaConfig) -> None:
+    if cfg.norm not in NORM_KINDS:
+        raise ValueError(f"LlamaConfig.norm must be one of {NORM_KINDS}, got {cfg.norm!r}")
+    if cfg.norm == "fused" and (cfg.d % 8 or not 8 <= cfg.d <= RMS_NORM_MAX_D):
+        raise ValueError(f'norm="fused" needs d to be a multiple of 8 in [8, {RMS_NORM_MAX_D}], got {cfg.d}')
+
+
 class LlamaBlock(torch.nn.Module):
     def __init__(self, cfg: LlamaConfig, tp, seed: int, device, dtype=torch.bfloat16, cp=None, rope_table=None):
         super().__init__()
@@ -126,6 +141,7 @@ class LlamaBlock(torch.nn.Module):
         self.cfg = cfg
         self.cp = cp  # context-parallel communicator: x holds this rank's shard of the sequence
         _check_rope_config(cfg)
+        _check_norm_config(cfg)
         if cfg.rope and rope_table is None:
             raise ValueError("LlamaConfig.rope needs the model's cos / sin table (rope_table)")
         self.rope_table = rope_table if cfg.rope else None  # shared by every block: a plain attribute, no buffer
@@ -157,22 +173,44 @@ class LlamaBlock(torch.nn.Module):
             raise ValueError(f"rope: {self.cp_size} x {seq} positions exceed LlamaConfig.max_positions = "
                              f"{cfg.max_positions}")
 
-    def forward(self, x, batch: int, seq: int, cu_seqlens: Optional[torch.Tensor] = None):
+    def _enter(self, x, addend):
+        """(residual stream, attn_norm of it).  norm="fused": the previous block's pending addend is
+        added by this norm's kernel."""
+        if self.cfg.norm != "fused":
+            return x, self.attn_norm(x)
+        if addend is None:
+            return x, rms_norm(x, self.attn_norm.weight, self.attn_norm.eps)
+        return add_rms_norm(x, addend, self.attn_norm.weight, self.attn_norm.eps)
+
+    def _leave(self, x, attn_out):
+        """The block's second half.  norm="fused": the pair (residual stream, pending addend), the
+        MLP output left for the next norm to add."""
+        if self.cfg.norm != "fused":
+            h = x + attn_out
+            return h + self.mlp(self.mlp_norm(h))
+        h, n = add_rms_norm(x, attn_out, self.mlp_norm.weight, self.mlp_norm.eps)
+        return h, self.mlp(n)
+
+    def forward(self, x, batch: int, seq: int, cu_seqlens: Optional[torch.Tensor] = None, addend=None):
+        """norm="torch": the block's output.  norm="fused": takes the pair (``x``, ``addend``: the
+        residual stream and what is still to be added to it, None at the first block) and returns
+        such a pair."""
         cfg = self.cfg
+        if addend is not None and cfg.norm != "fused":
+            raise ValueError('a pending addend needs norm="fused"')
         hd, hq, hkv = cfg.head_dim, self.heads, self.kv_heads
         self.check_positions(seq, cu_seqlens)  # before any launch of this block
         if cu_seqlens is not None:  # packed documents: boundaries on the flattened batch * seq token axis
             if cfg.attention != "flash" or self.cp is not None:
                 raise ValueError('cu_seqlens needs attention="flash" and no context parallelism (cp), got '
                                  f"attention={cfg.attention!r}, cp {'set' if self.cp is not None else 'None'}")
-            n = self.attn_norm(x)
+            x, n = self._enter(x, addend)
             q, k = self.wq(n).view(batch * seq, hq, hd), self.wk(n).view(batch * seq, hkv, hd)
             if cfg.rope:  # a token's position is its index inside its document
                 q, k = rope(q, k, self.rope_table, cu_seqlens=cu_seqlens)
             o = flash_attention_varlen(q, k, self.wv(n).view(batch * seq, hkv, hd), cu_seqlens, causal=True)
-            h = x + self.wo(o.view(batch * seq, hq * hd))
-            return h + self.mlp(self.mlp_norm(h))
-        n = self.attn_norm(x)
+            return self._leave(x, self.wo(o.view(batch * seq, hq * hd)))
+        x, n = self._enter(x, addend)
         if cfg.attention == "flash":  # the projections' views as they are; K and V stay at kv_heads
             q, k, v = (self.wq(n).view(batch, seq, hq, hd), self.wk(n).view(batch, seq, hkv, hd),
                        self.wv(n).view(batch, seq, hkv, hd))
@@ -182,8 +220,7 @@ class LlamaBlock(torch.nn.Module):
                 o = context_parallel_attention(self.cp, q, k, v, causal=True)
             else:
                 o = flash_attention(q, k, v, causal=True)
-            h = x + self.wo(o.view(batch * seq, hq * hd))
-            return h + self.mlp(self.mlp_norm(h))
+            return self._leave(x, self.wo(o.view(batch * seq, hq * hd)))
         q, k = self.wq(n).view(batch, seq, hq, hd), self.wk(n).view(batch, seq, hkv, hd)
         if cfg.rope:
             q, k = rope(q, k, self.rope_table)
@@ -195,8 +232,7 @@ class LlamaBlock(torch.nn.Module):
             v = v.repeat_interleave(rep, dim=1)
         o = F.scaled_dot_product_attention(q, k, v, is_causal=True)
         o = o.transpose(1, 2).reshape(batch * seq, hq * hd)
-        h = x + self.wo(o)
-        return h + self.mlp(self.mlp_norm(h))
+        return self._leave(x, self.wo(o))
 
 
 class LlamaModel(torch.nn.Module):
@@ -214,6 +250,7 @@ class LlamaModel(torch.nn.Module):
         self.vocab = vocab
         self.tp = tp
         _check_rope_config(cfg)
+        _check_norm_config(cfg)
         if cfg.loss not in LOSS_KINDS:
             raise ValueError(f"LlamaConfig.loss must be one of {LOSS_KINDS}, got {cfg.loss!r}")
         if vocab and cfg.loss == "torch" and _size_rank(tp)[0] > 1:
@@ -240,9 +277,16 @@ class LlamaModel(torch.nn.Module):
         for blk in self.blocks[:1]:  # a sequence beyond max_positions is refused before the embedding runs
             blk.check_positions(s, cu_seqlens)
         x = self.embed(ids).view(b * s, self.cfg.d) if self.vocab else x0
-        for blk in self.blocks:
-            x = blk(x, b, s, cu_seqlens)
-        x = self.norm(x)
+        if self.cfg.norm == "fused":  # every residual add happens in the norm that follows it
+            addend = None
+            for blk in self.blocks:
+                x, addend = blk(x, b, s, cu_seqlens, addend)
+            x = (rms_norm(x, self.norm.weight, self.norm.eps) if addend is None
+                 else add_rms_norm(x, addend, self.norm.weight, self.norm.eps)[1])
+        else:
+            for blk in self.blocks:
+                x = blk(x, b, s, cu_seqlens)
+            x = self.norm(x)
         if not self.vocab:
             return x.float().pow(2).mean()
         logits = self.head(x)
