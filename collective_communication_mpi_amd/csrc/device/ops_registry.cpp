@@ -17,6 +17,7 @@ void register_flash_attn_ops(pybind11::module_& m);
 void register_xent_ops(pybind11::module_& m);
 void register_rope_ops(pybind11::module_& m);
 void register_rmsnorm_ops(pybind11::module_& m);
+void register_optim_ops(pybind11::module_& m);
 
 void register_ops(pybind11::module_& m) {
   register_layout_ops(m);
@@ -32,6 +33,7 @@ void register_ops(pybind11::module_& m) {
   register_xent_ops(m);
   register_rope_ops(m);
   register_rmsnorm_ops(m);
+  register_optim_ops(m);
 }
 
 }  // namespace dev

@@ -2136,3 +2136,280 @@ def rms_norm_backward_reference(dy, h, weight, eps: float, dres=None):
     if dres is not None:
         dh = dh + dres.double()
     return dh, (dyd * n).sum(dim=0)
+
+
+# ---------------------------------------------------------------------------
+# AdamW with on-device gradient-norm clipping over flat buckets (csrc/device/optim.hip)
+# ---------------------------------------------------------------------------
+OPTIM_CHUNK = 2048          # elements per slot (csrc/device/optim.hpp kOptimChunk): 256 threads x 8
+OPTIM_MAX_GRID = 4096       # kOptimMaxGrid
+OPTIM_MAX_SEGS = 1 << 24    # kOptimMaxSegs
+OPTIM_MAX_ELEMS = 1 << 40   # kOptimMaxElems
+OPTIM_DECAY = 1             # seg_flags bit 0: weight decay applies
+OPTIM_SHARDED = 2           # seg_flags bit 1: counted in the "sharded" norm sum
+_OPTIM_DTYPES = (torch.bfloat16, torch.float32)
+
+
+def optim_slots(n: int, S: int, chunk: int = OPTIM_CHUNK) -> int:
+    """Slots of a bucket of ``n`` elements in ``S`` segments: ``n // chunk + S`` (the length of
+    the ``partials`` workspace)."""
+    return int(n) // int(chunk) + int(S)
+
+
+def optim_tile_map(seg_off, chunk: int = OPTIM_CHUNK, slots=None):
+    """Host mirror of the optimizer kernels' slot map: one entry per slot, ``(segment, begin,
+    end)`` for the workgroup pass that covers elements ``[begin, end)`` of the bucket, all inside
+    that segment, ``None`` for a spare slot.  ``seg_off`` is a CPU tensor or a list of ``S + 1``
+    offsets.  As in the kernel: segment ``i`` owns the slots from ``seg_off[i] // chunk + i`` on,
+    there are ``n // chunk + S`` slots, and a slot's segment is found by bisection.  ``slots``: an
+    iterable of slot numbers to map instead of all of them (a table of 2^33 elements has 4 M)."""
+    off = [int(x) for x in (seg_off.tolist() if isinstance(seg_off, torch.Tensor) else seg_off)]
+    chunk, S = int(chunk), len(off) - 1
+    if chunk < 1 or S < 1:
+        raise ValueError("optim_tile_map: chunk must be positive and seg_off hold at least 2 offsets")
+    n = off[-1]
+    if off[0] != 0 or any(off[i + 1] <= off[i] for i in range(S)):
+        raise ValueError("optim_tile_map: seg_off must start at 0 and increase strictly")
+    total = n // chunk + S
+    out = []
+    for slot in (range(total) if slots is None else slots):
+        slot = int(slot)
+        if not 0 <= slot < total:
+            raise ValueError(f"optim_tile_map: slot {slot} outside [0, {total})")
+        lo, hi = 0, S
+        while hi - lo > 1:
+            mid = (lo + hi) >> 1
+            if off[mid] // chunk + mid <= slot:
+                lo = mid
+            else:
+                hi = mid
+        b = off[lo] + (slot - (off[lo] // chunk + lo)) * chunk
+        out.append(None if b >= off[lo + 1] else (lo, b, min(b + chunk, off[lo + 1])))
+    return out
+
+
+def _optim_flat(name: str, t, dtypes, n=None, device=None, align: int = 16):
+    if not isinstance(t, torch.Tensor) or t.dtype not in dtypes:
+        raise TypeError(f"optim: {name} must be {' or '.join(str(d) for d in dtypes)}, got "
+                        f"{getattr(t, 'dtype', type(t).__name__)}")
+    if t.dim() != 1 or not t.is_contiguous() or t.numel() < 1:
+        raise ValueError(f"optim: {name} must be a contiguous 1-D tensor, got shape {tuple(t.shape)}")
+    if n is not None and t.numel() != n:
+        raise ValueError(f"optim: {name} must hold {n} elements, got {t.numel()}")
+    if device is not None and t.device != device:
+        raise ValueError(f"optim: {name} is on {t.device}, expected {device}")
+    if t.data_ptr() % align:
+        raise ValueError(f"optim: {name} must start at a {align}-byte-aligned address")
+
+
+def _optim_small(name: str, t, dtype, shape, device):
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+        raise TypeError(f"optim: {name} must be {dtype}, got {getattr(t, 'dtype', type(t).__name__)}")
+    if tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"optim: {name} must be a contiguous {tuple(shape)} tensor, got {tuple(t.shape)}")
+    if t.device != device:
+        raise ValueError(f"optim: {name} is on {t.device}, expected {device}")
+
+
+def _optim_sums_rules(sums, device, bucket=None):
+    if not isinstance(sums, torch.Tensor) or sums.dtype != torch.float64:
+        raise TypeError(f"optim: sums must be float64, got {getattr(sums, 'dtype', type(sums).__name__)}")
+    if sums.dim() != 2 or sums.shape[0] != 2 or sums.shape[1] < 1 or sums.stride(1) != 1:
+        raise ValueError(f"optim: sums must be [2, buckets] with unit column stride, got {tuple(sums.shape)}")
+    if sums.shape[1] > (1 << 20):
+        raise ValueError("optim: at most 2^20 buckets")
+    if sums.device != device:
+        raise ValueError(f"optim: sums is on {sums.device}, expected {device}")
+    if bucket is not None and not (isinstance(bucket, int) and 0 <= bucket < sums.shape[1]):
+        raise ValueError(f"optim: bucket {bucket!r} outside [0, {sums.shape[1]})")
+
+
+def optim_validate(g, seg_off, seg_ptr=None, seg_flags=None, p32=None, m=None, v=None, partials=None, sums=None,
+                   bucket: int = 0, clip=None, sched=None, betas=(0.9, 0.999), eps: float = 1e-8, max_grid: int = 0):
+    """Argument rules of the optimizer ops that need no GPU; raises TypeError (dtypes) / ValueError
+    (the rest) and returns ``(n, S)``.  ``g`` is the bucket: 1-D contiguous bf16 or fp32, 16-byte
+    aligned, ``1 <= n <= 2^40``.  ``seg_off`` [S + 1] int64, ``seg_ptr`` [S] int64 and ``seg_flags``
+    [S] int32 are contiguous tensors on ``g``'s device, ``1 <= S <= min(n, 2^24)``; a ``seg_off``
+    that lives on the CPU is also read: it starts at 0, increases strictly and ends at ``n`` (a
+    device table is the caller's promise: the call never synchronises).  ``p32`` (bf16 buckets
+    only; an fp32 parameter is its own master), ``m``, ``v``: fp32 [n], contiguous, 16-byte aligned.
+    ``partials``: fp32, at least ``n // OPTIM_CHUNK + S`` elements.  ``sums``: fp64 [2, buckets]
+    with unit column stride, ``bucket`` a column of it.  ``clip``: fp32 [2]; ``sched``: fp32 [4].
+    ``betas`` in [0, 1), ``eps`` non-negative and finite, ``max_grid`` in [0, 4096] (0: automatic)."""
+    _optim_flat("the gradient bucket", g, _OPTIM_DTYPES)
+    n, dev = g.numel(), g.device
+    if n > OPTIM_MAX_ELEMS:
+        raise ValueError(f"optim: 1 <= n <= 2^40 required, got {n}")
+    if not isinstance(seg_off, torch.Tensor) or seg_off.dtype != torch.int64:
+        raise TypeError(f"optim: seg_off must be int64, got {getattr(seg_off, 'dtype', type(seg_off).__name__)}")
+    if seg_off.dim() != 1 or not seg_off.is_contiguous() or seg_off.numel() < 2:
+        raise ValueError(f"optim: seg_off must be a contiguous [S + 1] tensor, got shape {tuple(seg_off.shape)}")
+    S = seg_off.numel() - 1
+    if S > min(n, OPTIM_MAX_SEGS):
+        raise ValueError(f"optim: 1 <= S <= min(n, 2^24) required, got S = {S}, n = {n}")
+    if seg_off.device.type == "cpu":
+        off = seg_off.tolist()
+        if off[0] != 0 or off[-1] != n or any(off[i + 1] <= off[i] for i in range(S)):
+            raise ValueError(f"optim: seg_off must start at 0, increase strictly and end at n = {n}")
+    if seg_off.device != dev:
+        raise ValueError(f"optim: seg_off is on {seg_off.device}, expected {dev}")
+    for name, t, dt in (("seg_ptr", seg_ptr, torch.int64), ("seg_flags", seg_flags, torch.int32)):
+        if t is not None:
+            _optim_small(name, t, dt, (S,), dev)
+    f32 = g.dtype == torch.float32
+    if f32 and p32 is not None:
+        raise ValueError("optim: an fp32 bucket has no p32: the parameter is its own master")
+    for name, t in (("p32", p32), ("m", m), ("v", v)):
+        if t is not None:
+            _optim_flat(name, t, (torch.float32,), n, dev)
+    if partials is not None:
+        _optim_flat("partials", partials, (torch.float32,), None, dev, 4)
+        if partials.numel() < optim_slots(n, S):
+            raise ValueError(f"optim: partials must hold n // {OPTIM_CHUNK} + S = {optim_slots(n, S)} elements, got "
+                             f"{partials.numel()}")
+    if sums is not None:
+        _optim_sums_rules(sums, dev, bucket)
+    if clip is not None:
+        _optim_small("clip", clip, torch.float32, (2,), dev)
+    if sched is not None:
+        _optim_small("sched", sched, torch.float32, (4,), dev)
+    _optim_hyper(betas, eps)
+    if isinstance(max_grid, bool) or not isinstance(max_grid, int) or not 0 <= max_grid <= OPTIM_MAX_GRID:
+        raise ValueError(f"optim: max_grid must be an int in [0, {OPTIM_MAX_GRID}], got {max_grid!r}")
+    return n, S
+
+
+def _optim_hyper(betas, eps) -> None:
+    if len(betas) != 2 or not all(isinstance(b, (int, float)) and not isinstance(b, bool) and 0.0 <= b < 1.0
+                                  for b in betas):
+        raise ValueError(f"optim: betas must be two floats in [0, 1), got {betas!r}")
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not 0.0 <= eps < float("inf"):
+        raise ValueError(f"optim: eps must be a non-negative finite float, got {eps!r}")
+
+
+def _optim_max_norm(max_norm) -> float:
+    if isinstance(max_norm, bool) or not isinstance(max_norm, (int, float)) or not 0.0 < max_norm < float("inf") \
+            or not 0.0 < torch.tensor(float(max_norm), dtype=torch.float32).item() < float("inf"):
+        raise ValueError(f"optim: max_norm must be a positive finite float, got {max_norm!r}")
+    return float(max_norm)
+
+
+def optim_sqsum(g, seg_off, seg_flags, partials, sums, bucket: int = 0, max_grid: int = 0):
+    """The first two levels of the gradient norm of one bucket.  ``k_optim_sqsum`` writes the fp32
+    sum of squares of every slot's gradients into ``partials[slot]`` (a fixed chain of 16 dependent
+    additions; a spare slot writes 0); ``k_optim_sums``, one workgroup, adds the partials in fp64 in
+    a fixed order into ``sums[0, bucket]`` (segments with ``OPTIM_SHARDED``) and ``sums[1, bucket]``
+    (the rest); ``sums=None`` stops after the first level.  No atomics: two calls give the same bits.  Every buffer is passed in: the call
+    allocates nothing, never synchronises with the host and can be captured in a graph.  Operands
+    as ``optim_validate`` describes; returns ``sums``."""
+    if seg_flags is None or partials is None:
+        raise ValueError("optim: optim_sqsum needs seg_flags and partials")
+    n, S = optim_validate(g, seg_off, None, seg_flags, partials=partials, sums=sums, bucket=bucket, max_grid=max_grid)
+    es = 8
+    _D().optim_sqsum(g.data_ptr(), g.dtype == torch.float32, seg_off.data_ptr(), seg_flags.data_ptr(), S, n,
+                     partials.data_ptr(), 0 if sums is None else sums.data_ptr() + bucket * es,
+                     0 if sums is None else sums.data_ptr() + (sums.stride(0) + bucket) * es, max_grid, _stream(g))
+    return sums
+
+
+def optim_clip(sums, max_norm: float, clip):
+    """``clip [2]`` fp32 = ``(norm, coef)`` from the ``[2, buckets]`` fp64 sums of squares (row 0
+    sharded, row 1 replicated): each row is added in bucket order, then the two totals; ``norm =
+    float(sqrt(total))`` and ``coef = min(1, max_norm / (norm + 1e-6))`` in fp32, the formula of
+    ``clip_grad_norm_``.  One thread (``k_optim_clip``); no allocation, no host synchronisation."""
+    if not isinstance(clip, torch.Tensor):
+        raise TypeError(f"optim: clip must be float32, got {type(clip).__name__}")
+    _optim_sums_rules(sums, clip.device)
+    _optim_small("clip", clip, torch.float32, (2,), sums.device)
+    max_norm = _optim_max_norm(max_norm)
+    _D().optim_clip(sums.data_ptr(), sums.data_ptr() + sums.stride(0) * sums.element_size(), sums.shape[1], max_norm,
+                    clip.data_ptr(), _stream(sums))
+    return clip
+
+
+def optim_adamw_update(g, seg_off, seg_ptr, seg_flags, p32, m, v, sched, clip=None, betas=(0.9, 0.999),
+                       eps: float = 1e-8, max_grid: int = 0):
+    """One AdamW step of a bucket (``k_optim_adamw``), per element, every operation rounded once::
+
+        g'  = g * coef                      (coef = clip[1]; skipped when clip is None)
+        m'  = (b1 * m) + (omb1 * g')
+        v'  = (b2 * v) + ((omb2 * g') * g')
+        p1  = p * decay if the segment has OPTIM_DECAY else p
+        p'  = p1 - lr * ((m' / bc1) / (sqrt(v' / bc2) + eps))
+
+    ``(lr, bc1, bc2, decay) = sched`` (``optim_sched``) and ``coef`` are read on the device, so a
+    captured graph of the call stays valid across steps.  A bf16 bucket keeps its master weights in
+    ``p32`` and the parameters at ``seg_ptr`` get ``bf16(p')``; an fp32 bucket (``p32=None``) updates
+    the parameters themselves.  ``m``, ``v`` (and ``p32``) are indexed like the bucket.  The
+    gradients are not written.  No allocation, no host synchronisation.  ``adamw_reference`` is the
+    mirror."""
+    if seg_ptr is None or seg_flags is None or m is None or v is None or sched is None:
+        raise ValueError("optim: optim_adamw_update needs seg_ptr, seg_flags, m, v and sched")
+    if isinstance(g, torch.Tensor) and g.dtype == torch.bfloat16 and p32 is None:
+        raise ValueError("optim: a bf16 bucket needs its fp32 master weights p32")
+    n, S = optim_validate(g, seg_off, seg_ptr, seg_flags, p32, m, v, clip=clip, sched=sched, betas=betas, eps=eps,
+                          max_grid=max_grid)
+    _D().optim_adamw(g.data_ptr(), g.dtype == torch.float32, seg_off.data_ptr(), seg_ptr.data_ptr(),
+                     seg_flags.data_ptr(), S, n, 0 if p32 is None else p32.data_ptr(), m.data_ptr(), v.data_ptr(),
+                     0 if clip is None else clip.data_ptr(), sched.data_ptr(), float(betas[0]), float(betas[1]),
+                     float(eps), max_grid, _stream(g))
+
+
+def optim_sched(lr: float, betas, weight_decay: float, t: int):
+    """What changes per step, as the kernel reads it: ``(lr, bc1, bc2, decay)`` with ``bc_i = 1 -
+    b_i^t`` and ``decay = 1 - lr * weight_decay``, each computed in fp64 and rounded once to fp32;
+    a CPU fp32 [4] tensor.  ``t >= 1`` is the number of the step."""
+    t = int(t)
+    if t < 1:
+        raise ValueError(f"optim_sched: t counts from 1, got {t}")
+    _optim_hyper(betas, 0.0)
+    lr, wd = float(lr), float(weight_decay)
+    if not (0.0 <= lr < float("inf")) or not (0.0 <= wd < float("inf")):
+        raise ValueError(f"optim_sched: lr and weight_decay must be non-negative and finite, got {lr}, {wd}")
+    vals = [lr, 1.0 - float(betas[0]) ** t, 1.0 - float(betas[1]) ** t, 1.0 - lr * wd]
+    return torch.tensor(vals, dtype=torch.float64).to(torch.float32)
+
+
+def adamw_reference(g, p, m, v, sched, coef=None, betas=(0.9, 0.999), eps: float = 1e-8, decays=True,
+                    dtype=torch.float32):
+    """The formula of ``optim_adamw_update`` in separate torch operations, in ``dtype``: returns
+    ``(p', m', v')``.  ``g``, ``p``, ``m``, ``v`` are tensors of one shape (any dtype: cast to
+    ``dtype`` first, which is exact for bf16 and fp32 inputs), ``sched`` the four values of
+    ``optim_sched`` (a tensor of any float dtype, cast to ``dtype``: fp64 values stay exact in the
+    fp64 mirror), ``coef`` a scalar or None (no clipping), ``decays`` a bool or a bool tensor of
+    that shape.  ``dtype=torch.float32`` on the CPU rounds every operation once, exactly like the
+    kernel: the bit-exact mirror (the constants are the kernel's: ``fl32(b)``, ``fl32(1 - b)``,
+    ``fl32(eps)``).  ``dtype=torch.float64`` is the exact formula from the same fp32 constants."""
+    def c(x):
+        return torch.tensor(float(x), dtype=torch.float64).to(torch.float32).to(dtype)
+
+    lr, bc1, bc2, decay = (torch.as_tensor(sched)[i].to(dtype) for i in range(4))
+    b1, omb1, b2, omb2, e = c(betas[0]), c(1.0 - betas[0]), c(betas[1]), c(1.0 - betas[1]), c(eps)
+    g, p, m, v = (x.to(dtype) for x in (g, p, m, v))
+    if coef is not None:
+        g = g * (coef.to(dtype) if isinstance(coef, torch.Tensor) else torch.tensor(float(coef), dtype=torch.float64).to(dtype))
+    m = (b1 * m) + (omb1 * g)
+    v = (b2 * v) + ((omb2 * g) * g)
+    if isinstance(decays, torch.Tensor):
+        p1 = torch.where(decays, p * decay, p)
+    else:
+        p1 = p * decay if decays else p
+    # torch's vectorised fp32 sqrt on the CPU is not correctly rounded (about 0.7 % of arguments are
+    # one ulp off); the fp64 root of an fp32 number, rounded to fp32, is
+    vh = v / bc2
+    root = torch.sqrt(vh) if dtype == torch.float64 else torch.sqrt(vh.double()).to(dtype)
+    p = p1 - lr * ((m / bc1) / (root + e))
+    return p, m, v
+
+
+def grad_norm_reference(grads, sharded=None):
+    """The gradient norm in fp64: ``grads`` is a list of tensors, ``sharded`` None or one bool per
+    tensor.  Returns ``(norm, sharded_sum, replicated_sum)`` as Python floats, the sums of squares."""
+    sh = rep = 0.0
+    for i, t in enumerate(grads):
+        s = float((t.detach().double() ** 2).sum().item())
+        if sharded is not None and sharded[i]:
+            sh += s
+        else:
+            rep += s
+    return (sh + rep) ** 0.5, sh, rep

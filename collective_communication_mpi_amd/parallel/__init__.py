@@ -9,6 +9,7 @@ from .layout import (  # noqa: F401
     device_group_for,
 )
 from .ddp import DistributedDataParallel, ddp_wrap  # noqa: F401,E402
+from .optim import AdamW  # noqa: F401,E402
 from .tensor_parallel import (  # noqa: F401,E402
     ColumnParallelLinear,
     ParallelSwiGLUMLP,
